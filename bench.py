@@ -1,6 +1,6 @@
 """EnCodec 24 kHz training throughput on MI355X (BASELINE.json metric).
 
-python bench.py [--gpus N] [--steps K] [--warmup W] [--config gen|gan]
+python bench.py [--gpus N] [--steps K] [--warmup W] [--config gen|gan|48k] [--full] [--dump-outputs DIR]
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 A step = one train_multi_gpu.py:train_one_step iteration on one batch of 32 synthetic 1 s clips
@@ -13,8 +13,14 @@ resident in HBM before the timed region. Rank 0 prints one JSON line.
 Steps replay HIP graphs at N = 1 (encx.train.Trainer(graphs=True): the step captured once
 after one eager step); at N > 1 the steps run eagerly (Trainer.step; ENCX_DP_GRAPHS=1 replays one
 graph per segment between the collectives, opt-in: DESIGN.md §6); --no-graphs steps eagerly.
-The warmup covers the eager step and the capture. The roofline / whole-step books come from a
-second, untimed, profiled pass of K eager steps (identical kernels).
+The warmup covers the eager step and the capture.
+
+A plain run sets up, warms up, times the K steps and prints the line (`roofline`, `whole_step`
+null, no `cpu_baseline`). --full adds what needs runs of its own: the roofline / whole-step
+books from a second, untimed, profiled pass of K eager steps (identical kernels; --no-roofline
+skips it) and the CPU baseline (--no-cpu-baseline skips it). --dump-outputs DIR writes the last
+timed step's results (dump_outputs below); inputs and initial weights are seeded, so two builds
+run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -46,8 +52,13 @@ def parse():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--config', choices=['gen', 'gan', '48k'], default='gan')
     ap.add_argument('--batch', type=int, default=32)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the profiled roofline / whole-step pass and the '
+                         'CPU baseline (a plain run times the steps and prints the headline line only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float32)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: skip the profiled pass')
     ap.add_argument('--no-graphs', action='store_true', help='eager steps instead of HIP-graph replay')
     ap.add_argument('--sync-codebooks', action='store_true',
                     help='all-reduce the RVQ EMA code sums across ranks (north_star DP; off = reference)')
@@ -91,6 +102,32 @@ def cpu_baseline(config, threads):
     return {'value': B * n / dt, 'unit': 'audio-seconds/sec', 'cores': threads, 'kind': 'port',
             'sample': f'oracle train step ({config}), {B} x 1 s clips, {n} timed steps after 1 warm-up, '
                       f'{dt:.1f} s wall on {threads} threads'}
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept of each flat parameter buffer (4 MB as float32)
+
+
+def dump_outputs(path, trainer, losses):
+    """--dump-outputs: what the last timed step handed its caller, one float32 DIR/<name>.npy
+    each: the step's returned losses (`loss_<key>`), the generator's output audio for the step's
+    batch (`y`), its RVQ codes (`codes`), and the weights the step left behind, generator and
+    discriminator (`params_gen`, `params_disc`): the same PCG64(4321) draw of DUMP_SAMPLE
+    positions of each flat buffer every run. Under 64 MB in all for every --config."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {f'loss_{k}': v.detach().reshape(-1) for k, v in (losses or {}).items()}
+    arrays['y'] = trainer.last_y
+    # every segment's codes [n_q, B*T] side by side (one segment at 24 kHz)
+    arrays['codes'] = torch.cat([c.reshape(c.shape[0], -1) for c, _ in trainer.model.seg_codes], 1)
+    for name, opt in (('params_gen', trainer.opt), ('params_disc', trainer.opt_d)):
+        if opt is None:
+            continue
+        flat = opt.flat
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.random.Generator(np.random.PCG64(4321)).integers(0, flat.numel(), DUMP_SAMPLE)
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays[name] = flat
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), t.detach().to('cpu', torch.float32).numpy())
 
 
 def main():
@@ -163,8 +200,9 @@ def main():
         torch.distributed.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for i in range(args.steps):
-        trainer.step(batches[i % 4])
+        last = trainer.step(batches[i % 4])
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
@@ -174,7 +212,9 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t)
-    prof = not args.no_roofline
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, last)  # before the profiled pass steps further
+    prof = args.full and not args.no_roofline
     if prof:
         # a second, untimed pass of the same K steps with the encx profiler on (eager: profiler
         # events are not graph-captured) books every kernel's algorithmic FLOPs / bytes and times
@@ -264,7 +304,7 @@ def main():
             out['config']['parallelism'] = f'dp{world} rehearsal: {world} ranks on 1 GPU over gloo'
         if force:
             out['config']['parallelism'] = 'dp1, the N > 1 step forced over a one-rank RCCL group (ENCX_DIST_FORCE)'
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # every host core this job may use: the process's CPU affinity, capped by the CPU share
             # the box grants a one-GPU job (OMP_NUM_THREADS, 16 on the pool's boxes; os.cpu_count()
             # there reports the whole machine, most of it not ours)

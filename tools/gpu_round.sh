@@ -22,7 +22,7 @@ for s in $STEPS; do
   case $s in
     tests) run tests 1500 python -m pytest tests -m gpu -q -rf --timeout 600 ${PYTEST_ARGS:-} ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 900 python bench.py ${BENCH_ARGS:-} ;;
-    prof) run prof 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline ${BENCH_ARGS:-} ;;
+    bench) run bench 900 python bench.py --full ${BENCH_ARGS:-} ;;
+    prof) run prof 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline ${BENCH_ARGS:-} ;;
   esac
 done
