@@ -9,8 +9,12 @@ reference's call order (so the same seed gives the same windows), and builds the
 [B][C][Tmax] batch with one `encx_crop_collate` launch. There is no CPU batch path.
 
 File decoding: PCM WAV through the standard library `wave` module (the image has no librosa
-or soundfile). It needs the model's sample rate (no resampler) and downmixes to mono by
-channel mean, as librosa.load(mono=True) does.
+or soundfile), `read_wav`. A file at the model's sample rate is downmixed to mono on the host by
+channel mean, as librosa.load(mono=True) does. A file at any other rate is resampled on the GPU
+while the pool is built, with the mono downmix fused (encx.utils.convert_audio, csrc/resample.hip).
+One deviation: the reference dataset resamples with librosa.load(sr=...), i.e. soxr, which cannot
+be reproduced here; this loader uses the filter of the reference's other loaders instead
+(utils.convert_audio: torchaudio.transforms.Resample's default windowed sinc).
 """
 import random
 import typing as tp
@@ -22,13 +26,11 @@ import torch
 from ._lib import call, stream, ensure_device
 
 
-def load_wav(path: str, sample_rate: int, mono: bool) -> np.ndarray:
-    """-> float32 [C][T] in [-1, 1). customAudioDataset.py:38-42 (librosa.load(sr, mono))."""
+def read_wav(path: str) -> tp.Tuple[np.ndarray, int]:
+    """-> (float32 [C][T] in [-1, 1), sample rate) of a PCM WAV file (8, 16 or 32 bits)."""
     with wave.open(path, 'rb') as w:
         sr, ch, width, n = w.getframerate(), w.getnchannels(), w.getsampwidth(), w.getnframes()
         raw = w.readframes(n)
-    if sr != sample_rate:
-        raise ValueError(f'{path}: sample rate {sr} != {sample_rate} (no resampler in encx)')
     if width == 2:
         x = np.frombuffer(raw, '<i2').astype(np.float32) / 32768.0
     elif width == 4:
@@ -37,23 +39,62 @@ def load_wav(path: str, sample_rate: int, mono: bool) -> np.ndarray:
         x = (np.frombuffer(raw, np.uint8).astype(np.float32) - 128.0) / 128.0
     else:
         raise ValueError(f'{path}: unsupported sample width {width}')
-    x = x.reshape(-1, ch).T
+    return np.ascontiguousarray(x.reshape(-1, ch).T, np.float32), sr
+
+
+def load_wav(path: str, sample_rate: int, mono: bool) -> np.ndarray:
+    """-> float32 [C][T] in [-1, 1) of a file at `sample_rate`. customAudioDataset.py:38-42
+    (librosa.load(sr, mono)) without the rate conversion: a file at another rate is refused here
+    (CustomAudioDataset resamples such files on the GPU)."""
+    x, sr = read_wav(path)
+    if sr != sample_rate:
+        raise ValueError(f'{path}: sample rate {sr} != {sample_rate} (load_wav does not resample)')
     if mono:
         x = x.mean(0, keepdims=True)
     return np.ascontiguousarray(x, np.float32)
 
 
+def load_clip(path: str, sample_rate: int, mono: bool, device) -> tp.Union[np.ndarray, torch.Tensor]:
+    """One file of the dataset: load_wav's host array at the model's rate, else the file
+    resampled to `sample_rate` on `device` (mono: the mean over the channels, before the
+    filter) as a device tensor [C][T']."""
+    x, sr = read_wav(path)
+    if sr == sample_rate:
+        return np.ascontiguousarray(x.mean(0, keepdims=True) if mono else x, np.float32)
+    from .utils import convert_audio
+    return convert_audio(torch.from_numpy(x).to(device), sr, sample_rate, 1 if mono else x.shape[0])
+
+
 class AudioPool:
     """Decoded clips packed back to back in one device buffer; clip i is
-    [channels[i]][lengths[i]] at offsets[i]."""
+    [channels[i]][lengths[i]] at offsets[i]. Clips may be host arrays or device tensors (files
+    resampled on the GPU). With any device tensor among them the pool is one torch.cat of the
+    per-clip tensors, so building it needs twice the pool's memory for a moment, and every such
+    file was its own upload and resample launch; a pool of host arrays alone goes up in one copy."""
 
-    def __init__(self, clips: tp.Sequence[np.ndarray], device='cuda'):
+    def __init__(self, clips: tp.Sequence[tp.Union[np.ndarray, torch.Tensor]], device='cuda'):
         self.device = torch.device(device)
-        arrs = [a[None] if a.ndim == 1 else a for a in (np.asarray(c, np.float32) for c in clips)]
+        arrs = [a[None] if a.ndim == 1 else a
+                for a in (c if torch.is_tensor(c) else np.asarray(c, np.float32) for c in clips)]
         self.channels = np.array([a.shape[0] for a in arrs], np.int64)
         self.lengths = np.array([a.shape[1] for a in arrs], np.int64)
         sizes = self.channels * self.lengths
         self.offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+        if any(torch.is_tensor(a) for a in arrs):
+            # clips already on the device (resampled there) stay there; host runs go up in one copy each
+            parts, run = [], []
+            for a in arrs:
+                if torch.is_tensor(a):
+                    if run:
+                        parts.append(torch.from_numpy(np.concatenate(run)).to(self.device))
+                        run = []
+                    parts.append(a.detach().to(self.device, torch.float32).reshape(-1))
+                else:
+                    run.append(a.reshape(-1))
+            if run:
+                parts.append(torch.from_numpy(np.concatenate(run)).to(self.device))
+            self.data = torch.cat(parts)
+            return
         flat = np.concatenate([a.reshape(-1) for a in arrs]) if arrs else np.zeros(0, np.float32)
         self.data = torch.from_numpy(flat).to(self.device)
 
@@ -87,7 +128,8 @@ class AudioPool:
 class CustomAudioDataset:
     """customAudioDataset.py:15-69 over an AudioPool. `config` carries the reference's fields
     (datasets.train_csv_path / test_csv_path, fixed_length, tensor_cut, model.sample_rate,
-    model.channels); `clips` may be given directly instead of reading the csv's files."""
+    model.channels); `clips` may be given directly instead of reading the csv's files. A listed
+    file whose rate differs from model.sample_rate is resampled on the device (load_clip)."""
 
     def __init__(self, config, transform=None, mode='train', clips=None, device='cuda'):
         assert mode in ['train', 'test'], 'dataset mode must be train or test'
@@ -100,7 +142,7 @@ class CustomAudioDataset:
             import pandas as pd
             csv = config.datasets.train_csv_path if mode == 'train' else config.datasets.test_csv_path
             files = pd.read_csv(csv, on_bad_lines='skip').iloc[:, 0].tolist()
-            clips = [load_wav(f, self.sample_rate, self.channels == 1) for f in files]
+            clips = [load_clip(f, self.sample_rate, self.channels == 1, device) for f in files]
         self.pool = AudioPool(clips, device=device)
 
     def __len__(self):

@@ -7,6 +7,7 @@ import contextlib
 import ctypes
 import os
 import math
+import operator
 
 import numpy as np
 import torch
@@ -1381,3 +1382,87 @@ def unpack_codes(data, K, T, bits):
     call('encx_bitunpack', data.data_ptr(), data.shape[1], Fn, K, T, int(bits), codes.data_ptr(),
          K * T, T, 1, stream())
     return codes
+
+
+# ---------------------------------------------------------------------------- resampling
+_RESAMPLE_CACHE = {}
+
+
+def _rate(v, name):
+    try:
+        r = operator.index(v)
+    except TypeError:
+        raise ValueError(f'encx: {name} must be a positive integer sample rate (got {v!r})') from None
+    if r <= 0 or r > 2 ** 31 - 1:
+        raise ValueError(f'encx: {name} must be a positive integer sample rate (got {v!r})')
+    return r
+
+
+def resample_geometry(orig, new):
+    """(o, n, width, taps, W) of torchaudio.transforms.Resample(orig, new) (encx.h): the reduced
+    rates, the filter half-width in input samples, the taps per phase of the full table and the
+    taps the compact table keeps."""
+    orig, new = _rate(orig, 'orig'), _rate(new, 'new')
+    g = math.gcd(orig, new)
+    o, n = orig // g, new // g
+    width = math.ceil(6 * o / (min(o, n) * 0.99))
+    return o, n, width, 2 * width + o, 2 * width + 1
+
+
+def resample_out_len(L, orig, new):
+    """ceil(n L / o) (encx_resample_out_len)."""
+    _rate(orig, 'orig'), _rate(new, 'new')
+    r = int(lib.encx_resample_out_len(int(L), int(orig), int(new)))
+    if r < 0:
+        raise ValueError(f'encx: no output length for L {L}, {orig} -> {new}')
+    return r
+
+
+def resample_table(orig, new, full=False):
+    """The host table of encx_resample_table: (coef float32 [n][W], start int32 [n]), or with
+    `full` its expanded form [n][taps] (table[p][start[p] + k] = coef[p][k], 0 elsewhere)."""
+    o, n, width, taps, W = resample_geometry(orig, new)
+    words = int(lib.encx_resample_table_floats(int(orig), int(new)))
+    if words < 0:
+        raise ValueError(f'encx: the rate pair {orig} -> {new} (reduced {o} -> {n}) is outside what '
+                         'encx_resample supports (encx.h)')
+    assert words == n * (W + 1)
+    buf = np.empty(words, np.float32)
+    call('encx_resample_table', buf.ctypes.data, int(orig), int(new))
+    coef, start = buf[:n * W].reshape(n, W), buf[n * W:].view(np.int32)
+    if not full:
+        return buf, coef, start
+    tab = np.zeros((n, taps), np.float32)
+    for p in range(n):
+        tab[p, start[p]:start[p] + W] = coef[p]
+    return tab
+
+
+def resample(x, orig, new, channels=None):
+    """convert_audio's device work (utils.py:84-97) in one launch: x [..., C, L] -> [...,
+    channels or C, ceil(n L / o)] by torchaudio.transforms.Resample(orig, new)'s default filter,
+    with the channel conversion fused (C -> C, C -> 1 the mean before the filter, 1 -> 2 copies).
+    orig == new leaves the samples as they are."""
+    orig, new = _rate(orig, 'orig'), _rate(new, 'new')
+    if x.dim() < 2:
+        raise ValueError('encx: resample takes [..., C, L]')
+    C, L = int(x.shape[-2]), int(x.shape[-1])
+    Cout = C if channels is None else int(channels)
+    if not (Cout == C or Cout == 1 or (C == 1 and Cout == 2)) or C > 64:
+        raise ValueError(f'encx: impossible to convert from {C} to {Cout} channels')
+    _check(x)
+    lead = tuple(x.shape[:-2])
+    if orig == new:
+        if Cout == C:
+            return x
+        return x.mean(-2, keepdim=True) if Cout == 1 else x.expand(*lead, Cout, L)
+    key = (str(x.device), orig // math.gcd(orig, new), new // math.gcd(orig, new))
+    tab = _RESAMPLE_CACHE.get(key)
+    if tab is None:
+        tab = _RESAMPLE_CACHE[key] = torch.from_numpy(resample_table(orig, new)[0]).to(x.device)
+    x = x.contiguous()
+    B = math.prod(lead)
+    Lout = resample_out_len(L, orig, new)
+    y = torch.empty(*lead, Cout, Lout, device=x.device, dtype=torch.float32)
+    call('encx_resample', ptr(x), ptr(tab), ptr(y), B, C, Cout, L, orig, new, stream())
+    return y

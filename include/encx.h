@@ -536,6 +536,30 @@ int encx_crop_collate(const float* pool, const int64_t* offsets, const int64_t* 
                       const int64_t* src_channels, const int64_t* starts, const int64_t* out_len,
                       float* out, int64_t B, int64_t C, int64_t Tmax, encx_stream_t stream);
 
+/* ------------------------------------------------------ sample-rate conversion (utils.py:84-97)
+ * convert_audio: the channel conversion, then torchaudio.transforms.Resample(orig, new) with its
+ * defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99). With g = gcd(orig, new),
+ * o = orig/g, n = new/g, base = min(o, n) * 0.99, width = ceil(6 o / base), taps = 2 width + o:
+ *   y[i*n + p] = sum_t table[p][t] * x[i*o + t - width]      (x = 0 outside [0, L))
+ *   table[p][t] = sinc(pi tau) cos^2(pi tau / 12) base / o,  tau = clamp(((t - width)/o - p/n) base, -6, 6)
+ * for the Lout = ceil(n L / o) = encx_resample_out_len outputs of a row (-1 for a length or rate
+ * that is not positive / does not fit). Only the taps with |tau| < 6 of a phase are kept, at most
+ * W = 2 width + 1 consecutive ones (the others are ~4e-33 base/o): encx_resample_table fills a HOST
+ * array of encx_resample_table_floats(orig, new) = n (W + 1) words, [n][W] coefficients (fp64
+ * math, rounded once) followed by n int32 `start`, table[p][start[p] + k] = coef[p][k]; the caller
+ * uploads it. encx_resample: x [B][Cin][L] -> y [B][Cout][Lout] with Cout == Cin (every channel by
+ * itself), Cout == 1 (the mean over the Cin channels, taken before the filter) or Cin == 1,
+ * Cout == 2 (both outputs the one result); anything else, a rate <= 0 or orig == new (the caller
+ * keeps x) is ENCX_EINVAL, as are rate pairs whose input span of 256 outputs, about
+ * 256 o/n + 14 max(o/n, 1) + o samples, exceeds 10240, and tables above 2^26 words. One launch; an
+ * output is one fmaf chain over its own W inputs in tap order, so a row's bits do not depend on
+ * the batch around it. Channel counts <= 64. */
+int64_t encx_resample_out_len(int64_t L, int64_t orig, int64_t neu);
+int64_t encx_resample_table_floats(int64_t orig, int64_t neu);
+int encx_resample_table(float* host_table, int64_t orig, int64_t neu);
+int encx_resample(const float* x, const float* table, float* y, int64_t B, int64_t Cin, int64_t Cout, int64_t L,
+                  int64_t orig, int64_t neu, encx_stream_t stream);
+
 /* ------------------------------------------------------ LM entropy coding (use_lm=True)
  * LMModel (model.py:27-65) over StreamingTransformerEncoder (modules/transformer.py:62-119),
  * inference only, and the arithmetic coder of quantization/ac.py. Activations are [B][T][D]
