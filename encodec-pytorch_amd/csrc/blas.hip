@@ -15,6 +15,7 @@
 // workspace from then on; the path's first step is always eager).
 #include <hipblaslt/hipblaslt.h>
 
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -43,6 +44,9 @@ struct BlasDev {
 
 std::mutex g_blas_mu;
 BlasDev g_blas[64];
+// route counters (encx_blas_stats): library GEMMs issued, and calls that found option BLAS on
+// but got no GEMM out of the library (the caller then runs its own kernels)
+std::atomic<int64_t> g_blas_launched{0}, g_blas_declined{0};
 
 bool capturing(hipStream_t st) {
     hipStreamCaptureStatus s = hipStreamCaptureStatusNone;
@@ -90,11 +94,10 @@ BlasPlan make_plan(hipblasLtHandle_t h, bool ta, bool tb, int m, int n, int k, i
     return p;
 }
 
-}  // namespace
-
-int encx_sgemm(hipStream_t st, bool ta, bool tb, int m, int n, int k, const float* A, int lda, const float* B,
+// 0: the GEMM is on the stream
+int sgemm_run(hipStream_t st, bool ta, bool tb, int m, int n, int k, const float* A, int lda, const float* B,
                int ldb, float* C, int ldc, bool accumulate, int batch, int64_t sa, int64_t sb, int64_t sc) {
-    if (!encx_opt(OPT_BLAS) || m <= 0 || n <= 0 || k <= 0) return -1;
+    if (m <= 0 || n <= 0 || k <= 0) return -1;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
     std::lock_guard<std::mutex> lock(g_blas_mu);
@@ -119,4 +122,20 @@ int encx_sgemm(hipStream_t st, bool ta, bool tb, int m, int n, int k, const floa
     const hipblasStatus_t s = hipblasLtMatmul(d.h, p.op, &alpha, A, p.la, B, p.lb, &beta, C, p.lc, C, p.lc, &p.algo,
                                               p.ws ? d.ws : nullptr, p.ws, st);
     return s == HIPBLAS_STATUS_SUCCESS ? 0 : -1;
+}
+
+}  // namespace
+
+int encx_sgemm(hipStream_t st, bool ta, bool tb, int m, int n, int k, const float* A, int lda, const float* B,
+               int ldb, float* C, int ldc, bool accumulate, int batch, int64_t sa, int64_t sb, int64_t sc) {
+    if (!encx_opt(OPT_BLAS)) return -1;
+    const int rc = sgemm_run(st, ta, tb, m, n, k, A, lda, B, ldb, C, ldc, accumulate, batch, sa, sb, sc);
+    (rc ? g_blas_declined : g_blas_launched).fetch_add(1, std::memory_order_relaxed);
+    return rc;
+}
+
+extern "C" int encx_blas_stats(int64_t* launched, int64_t* declined) {
+    if (launched) *launched = g_blas_launched.load(std::memory_order_relaxed);
+    if (declined) *declined = g_blas_declined.load(std::memory_order_relaxed);
+    return 0;
 }

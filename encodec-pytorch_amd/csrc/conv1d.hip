@@ -1108,15 +1108,36 @@ static bool blas_big_ok(int64_t M, int64_t N, int64_t Kred) {
 // The reduction is cut into KB equal chunks (a strided batch of library GEMMs into KB product
 // slabs, summed in order in fp64 by the epilogue / reduce): one library accumulation chain over
 // all 4096 reduction elements (or 2400 positions) was 5-7x the error of plain fp32 in the config-3
-// step check. KB: up to 8, chunks of at least 256, at most 48 MB of slabs.
-static int blas_chunks(int64_t K, int64_t slab_elems) {
+// step check. KB: up to 8, chunks of at least 256, at most 48 MB of slabs. Where no count cuts the
+// reduction evenly (an odd batch's 7777 positions: one chain over them measured 8.6x plain fp32,
+// tests/test_gpu_gemm_routes.py case b) the first KB - 1 chunks are ceil(K / KB) long and the
+// last one takes the shorter rest, as a second library GEMM.
+struct BlasChunks {
+    int KB, kc, last;  // chunks, the length of the first KB - 1, the length of the last
+};
+static BlasChunks blas_chunks(int64_t K, int64_t slab_elems) {
+    const auto fits = [&](int c) { return (size_t)c * slab_elems * sizeof(float) <= (48ull << 20); };
     for (const int c : {8, 6, 4, 3, 2})
-        if (K % c == 0 && K / c >= 256 && (size_t)c * slab_elems * sizeof(float) <= (48ull << 20)) return c;
-    return 1;
+        if (K % c == 0 && K / c >= 256 && fits(c)) return {c, (int)(K / c), (int)(K / c)};
+    for (const int c : {8, 6, 4, 3, 2})
+        if (K / c >= 256 && fits(c)) {
+            const int kc = (int)cdiv(K, c);  // (K = q c + r, q >= 256 > c: (c - 1)(q + 1) < K, the rest is not empty)
+            return {c, kc, (int)(K - (int64_t)(c - 1) * kc)};
+        }
+    return {1, (int)K, (int)K};
+}
+// chunk c of the reduction: C slab c (m x n, ldc m, slabs sc apart) = A (m x k chunk, chunks sa
+// apart) op(B) (chunks sb apart), the equal chunks as one strided batch, an uneven last one after it
+static int blas_chunked_gemm(hipStream_t st, bool tb, int m, int n, const BlasChunks& ch, const float* A, int lda,
+                             const float* B, int ldb, float* C, int64_t sa, int64_t sb, int64_t sc) {
+    const int even = ch.last == ch.kc ? ch.KB : ch.KB - 1;
+    if (encx_sgemm(st, false, tb, m, n, ch.kc, A, lda, B, ldb, C, m, false, even, sa, sb, sc)) return -1;
+    if (even == ch.KB) return 0;
+    return encx_sgemm(st, false, tb, m, n, ch.last, A + even * sa, lda, B + even * sb, ldb, C + even * sc, m, false);
 }
 static size_t blas_flat_ws(int64_t M, int64_t N, int64_t Kred) {
     if (!blas_flat_ok(M, N, Kred) && !blas_big_ok(M, N, Kred)) return 0;
-    return (size_t)(N * Kred + (int64_t)blas_chunks(Kred, N * M) * N * M) * sizeof(float);
+    return (size_t)(N * Kred + (int64_t)blas_chunks(Kred, N * M).KB * N * M) * sizeof(float);
 }
 // out[n][k] = ld.b(k, n): a wave per 4 columns n, lanes along k (one (ci, tap) run per lane group)
 template <class Ld>
@@ -1158,9 +1179,9 @@ static int blas_flat_run(const Ld& ld, const Ep& ep, const float* wA, int M, int
     ENCX_CHECK_LAUNCH();
     // slab c of Cm (M x N, column-major) = wA (M x Kred, column-major: the weights [Kred][M]) Xc^T
     // over reduction chunk c
-    const int KB = blas_chunks(Kred, (int64_t)N * M), kc = Kred / KB;
-    if (encx_sgemm(st, false, false, M, N, kc, wA, M, Xc, Kred, Cm, M, false, KB, (int64_t)kc * M, kc,
-                   (int64_t)N * M))
+    const BlasChunks ch = blas_chunks(Kred, (int64_t)N * M);
+    const int KB = ch.KB;
+    if (blas_chunked_gemm(st, false, M, N, ch, wA, M, Xc, Kred, Cm, (int64_t)ch.kc * M, ch.kc, (int64_t)N * M))
         return -1;
     hipLaunchKernelGGL(gemm_epi_kernel<Ep>, dim3((unsigned)cdiv(M, 32), (unsigned)cdiv(N, 32)), dim3(256), 0, st,
                        ep, Cm, M, N, KB);
@@ -2580,7 +2601,7 @@ static bool blas_wgrad_ok(int64_t A, int64_t Tl, int64_t N, int64_t CK) {
 static size_t blas_wgrad_ws(int64_t B, int64_t A, int64_t Tl, int64_t C, int64_t K) {
     const int64_t N = B * Tl;
     if (!blas_wgrad_ok(A, Tl, N, C * K)) return 0;
-    return (size_t)(N * A + N * C * K + cdiv(N, WGB_ROWS) * A + blas_chunks(N, A * C * K) * A * C * K) *
+    return (size_t)(N * A + N * C * K + cdiv(N, WGB_ROWS) * A + blas_chunks(N, A * C * K).KB * A * C * K) *
            sizeof(float);
 }
 // Lt[b Tl + t][a] = act(L[b][a][t]), 32 x 32 tiles through LDS
@@ -2637,9 +2658,10 @@ static int blas_wgrad_run(const float* L, const float* R, float* dw, float* ws, 
     ENCX_CHECK_LAUNCH();
     // slab c (C K x A, column-major = [A][C][K]) = Rc (C K x N) Lt (A x N)^T over position chunk c,
     // then the slabs in order into dw (wgrad_reduce, fp64)
-    const int KB = blas_chunks(N, A * CK), kc = (int)(N / KB);
-    if (encx_sgemm(st, false, true, (int)CK, (int)A, kc, Rc, (int)CK, Lt, (int)A, slabs, (int)CK, false, KB,
-                   (int64_t)kc * CK, (int64_t)kc * A, A * CK))
+    const BlasChunks ch = blas_chunks(N, A * CK);
+    const int KB = ch.KB;
+    if (blas_chunked_gemm(st, true, (int)CK, (int)A, ch, Rc, (int)CK, Lt, (int)A, slabs, (int64_t)ch.kc * CK,
+                          (int64_t)ch.kc * A, A * CK))
         return -1;
     hipLaunchKernelGGL(wgrad_reduce, dim3((unsigned)cdiv(A * CK, 64)), dim3(256), 0, st, slabs, dw, A * CK, KB,
                        accumulate, nullptr, nullptr, (int)A, 0);

@@ -1218,23 +1218,36 @@ int encx_lstm_bwd_weight(const float* DA, const float* xt, const float* Y, float
     // else the own GEMM. The B T positions are cut into KB equal chunks of about 300 (a strided
     // batch: one slab [4H][2H] per chunk) summed in order by lstm_slab_reduce:
     // one library accumulation chain over all 2400 positions of config 3 was 5x the error of plain
-    // fp32 (test_lstm_vs_oracle), the chunked form is within it.
-    int KB = 0;
+    // fp32 (test_lstm_vs_oracle), the chunked form is within it. Where no count cuts the positions
+    // evenly and one chain would run over 128 or more of them (a prime B T), 8 or fewer chunks of
+    // ceil(B T / KB), at least 64, and the shorter rest as a last chunk in a library GEMM of its own.
+    int KB = 0, kc = 0;
     for (const int c : {8, 6, 5, 4, 3, 2, 1})
         if (M % c == 0 && M / c >= 64) {
             KB = c;
+            kc = M / c;
             break;
         }
+    if (KB == 1)
+        for (const int c : {8, 6, 5, 4, 3, 2})
+            if (M / c >= 64) {
+                KB = c;
+                kc = (int)cdiv(M, c);  // (M = q c + r, q >= 64 > c: (c - 1)(q + 1) < M, the rest is not empty)
+                break;
+            }
     bool lib = KB > 0 && H % 4 == 0 && (encx_opt(OPT_BLAS) & 1) && (size_t)KB * N4 * Nw <= wsl_main(B, T, H);
     if (lib) {
-        const int kc = M / KB;
+        const int last = M - (KB - 1) * kc, even = last == kc ? KB : KB - 1;
         float* xh = ws + (size_t)KB * N4 * Nw;
         hipLaunchKernelGGL(lstm_xh, dim3((unsigned)cdiv(2 * BTH / 4, 256)), dim3(256), 0, st, in, Y + layer * BTH, xh,
                            (int)T, (int)H, 2 * BTH / 4);
         ENCX_CHECK_LAUNCH();
         // slab c (2H x 4H, column-major = [4H][2H]) = xh^T DA over position chunk c
-        lib = encx_sgemm(st, false, true, Nw, N4, kc, xh, Nw, DAl, N4, ws, Nw, false, KB, (int64_t)kc * Nw,
+        lib = encx_sgemm(st, false, true, Nw, N4, kc, xh, Nw, DAl, N4, ws, Nw, false, even, (int64_t)kc * Nw,
                          (int64_t)kc * N4, (int64_t)N4 * Nw) == 0;
+        if (lib && even < KB)
+            lib = encx_sgemm(st, false, true, Nw, N4, last, xh + (int64_t)even * kc * Nw, Nw,
+                             DAl + (int64_t)even * kc * N4, N4, ws + (int64_t)even * N4 * Nw, Nw, false) == 0;
         if (lib) {
             hipLaunchKernelGGL(lstm_slab_reduce, dim3((unsigned)cdiv((int64_t)N4 * Nw, 64)), dim3(256), 0, st, ws,
                                KB, (int)H, dw_ih, dw_hh, acc);

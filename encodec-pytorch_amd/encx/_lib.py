@@ -159,6 +159,15 @@ class option:
         return False
 
 
+def blas_stats():
+    """(launched, declined): the library's process-wide counts of plain GEMMs issued through
+    hipBLASLt and of those offered to it and handed back to the hand-written kernels (encx.h
+    encx_blas_stats). Read before and after a call to learn which side of option BLAS it took."""
+    a, b = ctypes.c_int64(), ctypes.c_int64()
+    call('encx_blas_stats', ctypes.byref(a), ctypes.byref(b))
+    return a.value, b.value
+
+
 def lstm_sync_errors():
     """Hand-off spins of the persistent LSTM kernels that timed out since the last call (encx.h
     encx_lstm_sync_errors; synchronises the device)."""

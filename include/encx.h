@@ -48,6 +48,12 @@ int encx_option_count(void);
 const char* encx_option_name(int i);  /* NULL past the last */
 int encx_get_option(const char* name, int64_t* value);
 int encx_set_option(const char* name, int64_t value, int64_t* previous /* may be NULL */);
+/* Which side of option BLAS the plain GEMMs ran on, counted since the library was loaded:
+ * *launched: GEMMs issued through hipBLASLt; *declined: GEMMs that a route with its BLAS bit on
+ * offered to hipBLASLt and got back (no algorithm for the problem, or the matmul call failed), so
+ * the hand-written kernels ran instead. Process-wide relaxed atomics, read-only here; either
+ * pointer may be NULL. A caller reads them before and after a call to learn its route. */
+int encx_blas_stats(int64_t* launched, int64_t* declined);
 /* Select the device; cheap, idempotent. */
 int encx_init(int device);
 /* Kernel timing for bench.py's roofline: while enabled, every launch of the named kernel

@@ -76,6 +76,22 @@ def test_host_only_queries():
     assert lib.encx_conv1d_fwd(*([None] * 6 + [0] * 12 + [None])) == 9001
 
 
+def test_blas_stats_is_a_host_query():
+    """encx_blas_stats reads the route counters without touching a device: both counts, either
+    pointer NULL, never negative, and unmoved by option changes (only encx_sgemm counts)."""
+    from encx import _lib as L
+    lib = _lib()
+    a, b = L.blas_stats()
+    assert a >= 0 and b >= 0
+    n = ctypes.c_int64(-1)
+    assert lib.encx_blas_stats(None, None) == 0
+    assert lib.encx_blas_stats(ctypes.byref(n), None) == 0 and n.value == a
+    assert lib.encx_blas_stats(None, ctypes.byref(n)) == 0 and n.value == b
+    with L.option(BLAS=0):
+        assert L.blas_stats() == (a, b)
+    assert L.get_option('BLAS') == int(os.environ.get('ENCX_BLAS', 3))
+
+
 def test_ops_refuse_cpu_tensors():
     from encx import ops
     x = torch.zeros(1, 1, 100)

@@ -55,10 +55,11 @@ def _layer_walk(seq, C, Tn, batch=B):
     return out
 
 
-def _fp64_layer(m, x64, act):
-    """The oracle's restatement of one layer on fp64 copies of the module's fp32 parameters."""
+def _fp64_layer(m, x64, act, dtype=torch.float64):
+    """The oracle's restatement of one layer on fp64 copies of the module's fp32 parameters
+    (dtype float32: the same restatement in plain fp32, x64 then being the fp32 input)."""
     from encx.modules.conv import SConv1d, SConvTranspose1d
-    p = {'m.' + k: v.detach().double().requires_grad_(True) for k, v in m.named_parameters()}
+    p = {'m.' + k: v.detach().to(dtype).requires_grad_(True) for k, v in m.named_parameters()}
     xin = F.elu(x64) if act == 'elu' else x64
     if isinstance(m, SConv1d):
         c = m.conv
@@ -81,7 +82,11 @@ def test_seanet_layers_b32_vs_fp64(stack):
     75 -- through the encx module the model runs (the fused block kernels at T >= 2048, the
     linked convs with the shortcut-join and residual epilogue below): output, input grad and
     every parameter grad within 2e-5 of the fp64 restatement, relative to the tensor's largest
-    magnitude (fp32 accumulation over up to 768 k positions per weight-grad element)."""
+    magnitude (fp32 accumulation over up to 768 k positions per weight-grad element). The two
+    layers of each stack with an input or output of T <= 128, whose GEMMs go to hipBLASLt by
+    default, run a second time under option BLAS 0 (the hand-written flattened GEMMs that a
+    declining hipBLASLt falls back to), against the same fp64 results and bound."""
+    from encx._lib import blas_stats, option
     from encx.model import EncodecModel
     from encx.modules.seanet import SEANetResnetBlock
     torch.manual_seed(11)
@@ -97,7 +102,7 @@ def test_seanet_layers_b32_vs_fp64(stack):
     seq = seq.to(DEV)
     walk = _layer_walk(seq, 1, 24000) if stack == 'encoder' else _layer_walk(seq, 128, 75)
     assert len(walk) == 10, len(walk)
-    bad = []
+    bad, n_short = [], 0
     for idx, m, act, shape in walk:
         torch.cuda.empty_cache()
         gen = torch.Generator(device=DEV).manual_seed(1000 + idx)
@@ -117,7 +122,29 @@ def test_seanet_layers_b32_vs_fp64(stack):
         name = f'{stack}.model.{idx} {type(m).__name__} {tuple(shape)}'
         print(name + ': ' + ' '.join(f'{k} {e:.1e}' for k, e in errs.items()))
         bad += [(name, k, e) for k, e in errs.items() if not e < 2e-5]
+        if min(shape[2], y.shape[2]) <= 128:
+            # the short-T layers (the k16 s8 stage, the T 75 k7 convs, the 512 -> 256 transposed
+            # conv) once more with option BLAS 0: their GEMMs on the library's own flattened
+            # kernels and k-split slabs instead of hipBLASLt, same fp64 results, same bound
+            n_short += 1
+            x0 = x.detach().clone().requires_grad_(True)
+            for prm in m.parameters():
+                prm.grad = None
+            before = blas_stats()
+            with option(BLAS=0):
+                y0 = m(x0) if isinstance(m, SEANetResnetBlock) else m(x0, act=act)
+                y0.backward(dy)
+                torch.cuda.synchronize()
+            assert blas_stats() == before, (name, 'BLAS 0 offered a GEMM to hipBLASLt', before, blas_stats())
+            errs = {'y': _rel(y0, y64), 'dx': _rel(x0.grad, x64.grad)}
+            for k, prm in m.named_parameters():
+                errs['d' + k] = _rel(prm.grad, p64['m.' + k].grad)
+            name += ' BLAS=0'
+            print(name + ': ' + ' '.join(f'{k} {e:.1e}' for k, e in errs.items()))
+            bad += [(name, k, e) for k, e in errs.items() if not e < 2e-5]
+            del x0, y0
         del x, y, dy, x64, y64, p64
+    assert n_short == 2, n_short
     assert not bad, bad
 
 

@@ -409,23 +409,54 @@ def test_normalize_and_scale():
 
 
 # --------------------------------------------------------------------------- LSTM
-@pytest.mark.parametrize('B,H,Tn,L,fuse,persist,wgs', [
+# (B, H, Tn, L, fuse, persist, wgs) at option BLAS's default: the weight grads of every call with
+# B T >= 64 run in hipBLASLt (csrc/lstm.hip encx_lstm_bwd_weight)
+_LSTM_ROWS = [
     (3, 32, 7, 1, 0, 1, 32), (17, 64, 20, 2, 0, 1, 32), (5, 48, 9, 3, 0, 1, 32), (32, 512, 75, 2, 0, 1, 32),
     (32, 512, 75, 2, 0, 0, 32), (17, 64, 20, 2, 1, 0, 32), (32, 512, 75, 2, 1, 0, 32), (17, 128, 20, 2, 0, 1, 32),
     (5, 256, 9, 3, 0, 1, 32), (40, 384, 11, 1, 0, 1, 32), (17, 256, 20, 2, 0, 1, 1),
     # batches above one launch's 64 rows: run as chunks (ops.lstm)
-    (80, 64, 12, 2, 0, 1, 32), (130, 128, 9, 1, 0, 1, 32), (96, 512, 6, 2, 0, 0, 32)])
-def test_lstm_vs_oracle(B, H, Tn, L, fuse, persist, wgs):
+    (80, 64, 12, 2, 0, 1, 32), (130, 128, 9, 1, 0, 1, 32), (96, 512, 6, 2, 0, 0, 32)]
+# (..., blas): the same with option BLAS set. BLAS 0: the own 128 x 128 GEMM -- one launch storing
+# straight into the grads (B T 340 has no room for a 256-deep split, whatever wgs says), 8 even
+# k-slabs through EpSlabs + lstm_slab_reduce (B T 2400), 2 slabs with a ragged second one (B T 520).
+# BLAS 3 at the position-chunk rule {8, 6, 5, 4, 3, 2, 1} with chunks >= 64: B T 340 -> KB 5 is
+# the (17, ., 20, .) rows above; a prime B T 67 -> KB 1, one library chain; B T 31 x 73 = 2263,
+# which no count divides -> 7 chunks of 283 and a last one of 282 in a GEMM of its own (one chain
+# over 2400 positions was 5x plain fp32's error); B T 63 is under the rule's floor and takes the
+# own GEMM whatever the option says.
+_LSTM_BLAS_ROWS = [
+    (17, 256, 20, 2, 0, 1, 32, 0), (17, 256, 20, 2, 0, 1, 1, 0), (32, 512, 75, 2, 0, 1, 32, 0),
+    (40, 64, 13, 1, 0, 1, 32, 0),
+    (1, 128, 67, 1, 0, 1, 32, 3), (31, 128, 73, 1, 0, 1, 32, 3), (9, 128, 7, 1, 0, 1, 32, 3)]
+
+
+def _lstm_lib_gemms(M):
+    """Library GEMMs of one layer's weight grad over M = B T positions with BLAS bit 1 on
+    (csrc/lstm.hip encx_lstm_bwd_weight): none below 64 positions; one strided batch where a
+    count of {8, 6, 5, 4, 3, 2} cuts M into equal chunks of 64+, or where M < 128 is one chunk;
+    else the equal chunks and the shorter last one, two."""
+    if M < 64:
+        return 0
+    return 1 if M < 128 or any(M % c == 0 and M // c >= 64 for c in (8, 6, 5, 4, 3, 2)) else 2
+
+
+@pytest.mark.parametrize('B,H,Tn,L,fuse,persist,wgs,blas', [
+    *(pytest.param(*r, None, id='-'.join(map(str, r))) for r in _LSTM_ROWS), *_LSTM_BLAS_ROWS])
+def test_lstm_vs_oracle(B, H, Tn, L, fuse, persist, wgs, blas):
     """encx LSTM (csrc/lstm.hip) forward + backward against the oracle's step-by-step
     restatement of SLSTM (modules/lstm.py:22-28) run in fp64 on the CPU, for 1, 2 and 3 layers:
     every output and grad within 4x the error of the same restatement run in plain fp32.
     persist: the one-launch recurrences (option LSTM_PERSIST; used where H % 128 == 0, H <= 512
     and the workgroups fit the CUs, else the launch-per-step wavefront); fuse: the opt-in fused
     backward step of the wavefront (option LSTM_FUSE); wgs: the weight grad's k-split cap
-    (LSTM_WG_SPLITS; 1 = one GEMM storing straight into the grads)."""
+    (LSTM_WG_SPLITS; 1 = one GEMM storing straight into the grads) of the own GEMM, which runs
+    under BLAS 0 and below 64 positions; blas: option BLAS (None: its default). Every row proves
+    its weight grads' route by encx_blas_stats: with bit 1 on, _lstm_lib_gemms library GEMMs per
+    layer of every batch chunk and none handed back; nothing offered to the library otherwise."""
     import ctypes
     from encx import ops
-    from encx._lib import option, call
+    from encx._lib import option, call, blas_stats
     gen = torch.Generator().manual_seed(B * 1000 + H)
     k = 1.0 / np.sqrt(H)
     names = ['weight_ih', 'weight_hh', 'bias_ih', 'bias_hh']
@@ -441,10 +472,22 @@ def test_lstm_vs_oracle(B, H, Tn, L, fuse, persist, wgs):
     y64 = O.slstm(x64, p64, 'm', L)
     (y64 * r64).sum().backward()
     x = x64.detach().float().to(DEV).requires_grad_(True)
-    with option(LSTM_FUSE=fuse, LSTM_PERSIST=persist, LSTM_WG_SPLITS=wgs):
+    opts = dict(LSTM_FUSE=fuse, LSTM_PERSIST=persist, LSTM_WG_SPLITS=wgs)
+    if blas is not None:
+        opts['BLAS'] = blas
+    torch.cuda.synchronize()
+    before = blas_stats()
+    with option(**opts):
         y = ops.lstm(x, wts, skip=True)
         (y * r64.float().to(DEV)).sum().backward()
         torch.cuda.synchronize()
+    after = blas_stats()
+    nchunks = -(-B // ops.LSTM_MAX_BATCH)
+    sizes = [B // nchunks + (i < B % nchunks) for i in range(nchunks)]  # ops.lstm's batch chunks
+    want = L * sum(_lstm_lib_gemms(b * Tn) for b in sizes) if (3 if blas is None else blas) & 1 else 0
+    moved = (after[0] - before[0], after[1] - before[1])
+    assert moved == (want, 0), (f'encx_blas_stats moved by (launched, declined) = {moved}, the intended route '
+                                f'moves it by ({want}, 0)')
     nerr = ctypes.c_int64()
     call('encx_lstm_sync_errors', ctypes.byref(nerr))
     assert nerr.value == 0, f'{nerr.value} hand-off spins timed out'
