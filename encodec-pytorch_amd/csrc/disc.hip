@@ -2581,11 +2581,32 @@ struct C2WgR {
 template <int KTW, int WQ>
 struct RwStage {  // one item's operands, loaded a whole item ahead of their MFMAs
     f32x4 av, yv, xw[KTW][WQ];
-    int p, col0;  // this lane's first position / first input column (for the edge masks)
-    int sha;      // the dy / y quad's shift (nonzero only at the very end of the tensor)
-    int xo[KTW];  // this lane's first window element offset per kt row (unclamped)
-    bool edge;    // wave-uniform: some element of this item lies outside its row
-    bool rok[KTW];
+};
+// Quad load at a wave-uniform base plus a 32-bit byte offset per lane (plus a constant). The base
+// is formed on the scalar unit; the lane's part is one 64-bit add per base (the compiler keeps the
+// zero-extended lane offset in a register pair), and the constant goes into the instruction.
+ENCX_DEV f32x4 ld4_sv(const float* base, uint32_t lane_bytes, int imm = 0) {
+    typedef const __attribute__((address_space(1))) char* gptr;
+    const uint64_t b = (uint64_t)base;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
+    const gptr p = (gptr)(((uint64_t)hi << 32) | lo);
+    return *(const __attribute__((address_space(1))) f32x4u*)(p + (uint64_t)lane_bytes + imm);
+}
+// An item's geometry is the same for every lane of the wave, so it lives in scalar registers and
+// is advanced from item to item (RwPos: + NW chunks, carrying at SW, T2, NCS; no division). A
+// lane's element offsets are these scalars plus a per-lane constant computed once per wave.
+struct RwPos {
+    int cs, t, strip, b;  // chunk in strip, row, strip, batch
+};
+template <int KTW>
+struct RwItem {
+    int f0;         // first position of the chunk
+    int sy;         // element offset of dy[b][0][t][f0]
+    int sx[KTW];    // element offset of x[b][0][row(k)][S f0 - pf] (row 0 if row(k) is outside)
+    bool edge;      // some element of this item lies outside its row
+    bool rok[KTW];  // kt row k is inside the input
+    bool ends;      // some lane's quad may start outside the tensor (its first / last quads only)
 };
 // NW > 1 (c2_wgrad_rwg): NW waves per workgroup share one (kt group, ci block, split) task and
 // take its items interleaved (wave w: items it_beg + w, + NW, ...; neighbouring waves read
@@ -2598,7 +2619,8 @@ __global__ __launch_bounds__(NW * 64, NW == 1 ? 2 : 1) void c2_wgrad_rw_kernel(C
     constexpr int NTAP = KTW * KF;
     static_assert(NW == 1 || NW == 8, "one-wave or 8-wave workgroups");
     const C2Geo g = a.g;
-    const int lane = threadIdx.x & 63, h = lane >> 5, l = lane & 31, wv = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, h = lane >> 5, l = lane & 31;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // uniform, and known to be
     const int id = xcd_linear_id();
     const int kg = id % a.ktg, rest = id / a.ktg, cb = rest % a.cib, split = rest / a.cib;
     const int kt0 = kg * KTW, ci = cb * 32 + l;
@@ -2612,57 +2634,104 @@ __global__ __launch_bounds__(NW * 64, NW == 1 ? 2 : 1) void c2_wgrad_rw_kernel(C
 #pragma unroll
     for (int j = 0; j < NTAP; ++j) acc[j] = (f32x16){0};
     float bsum = 0.f;
-    // ---- issue the loads of item it; nothing waits for them until compute(). Every quad is one
-    // (unaligned) load at its own address, so every item issues the same loads: elements past a
-    // row's ends read the neighbouring row (in bounds) and compute() zeroes them; only a quad
-    // past the END of the tensor is read from a clamped address and shifted.
-    auto load = [&](RwStage<KTW, WQ>& st, int it) {
-        // items run (b, strip, t, chunk in strip), the chunk fastest: the kt-group workgroups of a
-        // task (same ci block and split, same XCD) read the same dy / y quads at the same time and
-        // x rows one or two steps of t apart, a reuse distance of a strip's bytes, not a row's
-        const int cs = it % a.SW, r1 = it / a.SW, t = r1 % g.T2, r2 = r1 / g.T2;
-        const int c = (r2 % a.NCS) * a.SW + cs, b = r2 / a.NCS;
-        const int f0 = c * 8, p = f0 + 4 * h;
-        const int oa = (b * g.Co + (co_ok ? l : 0)) * plane_y + t * g.Fo + p;
-        const int oac = min(oa, ylast);
-        st.av = ld4u(a.dy + oac);
-        if (YM) st.yv = ld4u(a.yact + oac);
-        st.sha = oa - oac;
-        const int col0 = S * p - g.pf;
-        const int xb = (b * g.Ci + (ci_ok ? ci : 0)) * plane_x + col0;
+    // Items run (b, strip, t, chunk in strip), the chunk fastest: the kt-group workgroups of a
+    // task (same ci block and split, same XCD) read the same dy / y quads at the same time and
+    // x rows one or two steps of t apart, a reuse distance of a strip's bytes, not a row's
+    auto advance = [&](RwPos& q) {  // the wave's next item: NW chunks on
+        q.cs += NW;
+        while (q.cs >= a.SW) {
+            q.cs -= a.SW;
+            if (++q.t == g.T2) {
+                q.t = 0;
+                if (++q.strip == a.NCS) {
+                    q.strip = 0;
+                    ++q.b;
+                }
+            }
+        }
+    };
+    // this lane's constant part of its offsets: dy / y quad at it.sy + ly, window k at it.sx[k] + lx
+    const int ly = (co_ok ? l : 0) * plane_y + 4 * h;
+    const int lx = (ci_ok ? ci : 0) * plane_x + 4 * S * h;
+    // their largest values over the wave (scalars), for RwItem::ends
+    const int ly_max = (min(g.Co, 32) - 1) * plane_y + 4;
+    const int lx_max = min(g.Ci - 1, cb * 32 + 31) * plane_x + 4 * S;
+    // load_in's form (scalar base + 32-bit lane byte offset) needs the byte offsets of one image's
+    // lanes to fit in 32 bits; and its stand-in loads of an `ends` item (base 0, see step) stay
+    // inside the tensor if a plane holds the lanes' last quads. Otherwise: no lane offsets, and
+    // every item counts as `ends` (stand-in at the tensor's start, then load_any).
+    const bool sv_ok = g.Co * plane_y < (1 << 29) && g.Ci * plane_x < (1 << 29) && plane_y >= 8 &&
+                       plane_x >= 4 * S + 4 * WQ;
+    const uint32_t lyb = sv_ok ? 4u * (uint32_t)ly : 0u, lxb = sv_ok ? 4u * (uint32_t)lx : 0u;
+    auto item = [&](const RwPos& q) {
+        RwItem<KTW> it;
+        const int f0 = (q.strip * a.SW + q.cs) * 8;
+        it.f0 = f0;
+        it.sy = q.b * g.Co * plane_y + q.t * g.Fo + f0;
+        const int xb = q.b * g.Ci * plane_x + S * f0 - g.pf;
 #pragma unroll
         for (int k = 0; k < KTW; ++k) {
-            const int row = t + (kt0 + k) * g.dt - g.pt;
-            st.rok[k] = row >= 0 && row < g.T2;
-            const int rb = xb + (st.rok[k] ? row : 0) * g.Fi;
+            const int row = q.t + (kt0 + k) * g.dt - g.pt;
+            it.rok[k] = row >= 0 && row < g.T2;
+            it.sx[k] = xb + (it.rok[k] ? row : 0) * g.Fi;
+        }
+        it.edge = f0 + 8 > g.Fo || S * f0 - g.pf < 0 || S * (f0 + 4) - g.pf + 4 * WQ > g.Fi;
+        it.ends = !sv_ok || it.sy + ly_max > ylast;
+#pragma unroll
+        for (int k = 0; k < KTW; ++k) it.ends = it.ends || it.sx[k] < 0 || it.sx[k] + lx_max + 4 * (WQ - 1) > xlast;
+        return it;
+    };
+    // ---- issue the loads of an item; nothing waits for them until its compute. Every quad is one
+    // (unaligned) load at its own address, so every item issues the same loads: elements past a
+    // row's ends read the neighbouring row (in bounds) and compute() zeroes them; only a quad
+    // past the END of the tensor is read from a clamped address and shifted (load_any).
+    // An item with no edge reads only inside its rows: no clamp, and the address is the item's
+    // scalar base plus the lane's constant offset (no per-lane address arithmetic).
+    auto load_in = [&](RwStage<KTW, WQ>& st, const RwItem<KTW>& it) {
+        const int sy = it.ends ? 0 : it.sy;
+        st.av = ld4_sv(a.dy + sy, lyb);
+        if (YM) st.yv = ld4_sv(a.yact + sy, lyb);
+#pragma unroll
+        for (int k = 0; k < KTW; ++k) {
+            const int sx = it.ends ? 0 : it.sx[k];
+#pragma unroll
+            for (int w = 0; w < WQ; ++w) st.xw[k][w] = ld4_sv(a.x + sx, lxb, 16 * w);
+        }
+    };
+    auto load_any = [&](RwStage<KTW, WQ>& st, const RwItem<KTW>& it) {
+        const int oac = min(it.sy + ly, ylast);
+        st.av = ld4u(a.dy + oac);
+        if (YM) st.yv = ld4u(a.yact + oac);
+#pragma unroll
+        for (int k = 0; k < KTW; ++k) {
+            const int rb = it.sx[k] + lx;
 #pragma unroll
             for (int w = 0; w < WQ; ++w) st.xw[k][w] = ld4u(a.x + min(max(rb + 4 * w, 0), xlast));
-            st.xo[k] = rb;
         }
-        st.p = p;
-        st.col0 = col0;
-        st.edge = f0 + 8 > g.Fo || S * f0 - g.pf < 0 || S * (f0 + 4) - g.pf + 4 * WQ > g.Fi;
     };
-    // ---- the 9 taps x 4 positions of one item
-    auto compute = [&](RwStage<KTW, WQ>& st) {
-        if (st.edge) {
-            if (__any(st.sha != 0)) {
-                st.av = quad_abs(st.av, ylast + st.sha, ylast);
-                if (YM) st.yv = quad_abs(st.yv, ylast + st.sha, ylast);
+    // ---- what an item that is not interior needs before its MFMAs: the tensor's end quads moved
+    // into place, elements outside their row and the lanes of absent channels zeroed
+    auto fix = [&](RwStage<KTW, WQ>& st, const RwItem<KTW>& it) {
+        if (it.edge) {
+            const int p = it.f0 + 4 * h, col0 = S * p - g.pf;
+            const int oa = it.sy + ly;
+            if (__any(oa > ylast)) {  // (only at the very end of the tensor)
+                st.av = quad_abs(st.av, oa, ylast);
+                if (YM) st.yv = quad_abs(st.yv, oa, ylast);
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                if (st.p + e >= g.Fo) st.av[e] = 0.f;
+                if (p + e >= g.Fo) st.av[e] = 0.f;
 #pragma unroll
             for (int w = 0; w < WQ; ++w) {
 #pragma unroll
                 for (int k = 0; k < KTW; ++k) {  // the tensor's first / last quad
-                    const int o = st.xo[k] + 4 * w;
+                    const int o = it.sx[k] + lx + 4 * w;
                     if (__any(o < 0 || o > xlast)) st.xw[k][w] = quad_abs(st.xw[k][w], o, xlast);
                 }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const int col = st.col0 + 4 * w + e;
+                    const int col = col0 + 4 * w + e;
                     if (col < 0 || col >= g.Fi) {
 #pragma unroll
                         for (int k = 0; k < KTW; ++k) st.xw[k][w][e] = 0.f;
@@ -2678,36 +2747,82 @@ __global__ __launch_bounds__(NW * 64, NW == 1 ? 2 : 1) void c2_wgrad_rw_kernel(C
                 for (int w = 0; w < WQ; ++w)
                     if (!ci_ok) st.xw[k][w] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
+    };
+    // ---- dy' = dy LeakyReLU'(y) and the bias sum of one item. Not contracted: the sum adds the
+    // ROUNDED products, as it does when the producer has already applied the mask (YM false);
+    // beside the MFMAs of the same block the compiler otherwise fuses them (test_premask_bit_identical)
+    auto grad = [&](const RwStage<KTW, WQ>& st) {
+#pragma clang fp contract(off)
         f32x4 ca = st.av;
         if (YM) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) ca[e] *= lrelu_grad(st.yv[e]);
         }
         bsum += (ca[0] + ca[1]) + (ca[2] + ca[3]);
-#pragma unroll
-        for (int k = 0; k < KTW; ++k) {
-            if (!st.rok[k]) continue;  // a kt row outside the input contributes zero
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int kf = 0; kf < KF; ++kf) {
-                    const int r = S * q + kf;
-                    acc[k * KF + kf] = mfma32(ca[q], st.xw[k][r >> 2][r & 3], acc[k * KF + kf]);
-                }
-        }
+        return ca;
     };
-    // two register stages, alternating: item it + 1 is in flight while item it computes
-    // The prefetches are unconditional (past the end they re-load the last item and are never
-    // used), so every path issues the same loads and each wait is for exactly the older item.
+    // ---- the KF taps x 4 positions of kt row k
+    auto taps = [&](const RwStage<KTW, WQ>& st, const f32x4& ca, int k) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int kf = 0; kf < KF; ++kf) {
+                const int r = S * q + kf;
+                acc[k * KF + kf] = mfma32(ca[q], st.xw[k][r >> 2][r & 3], acc[k * KF + kf]);
+            }
+    };
+    // One step: issue the loads of item nx into stage sn, then the MFMAs of item cu in stage sc.
+    // With the middle kt row inside the input that is ONE basic block: the six loads (scalar base
+    // + lane offset), the LeakyReLU' products and the bias adds, then the row's MFMAs, with one
+    // wait for exactly the older item's loads. An item at an end of the tensor (nx.ends; a handful
+    // per launch) gets stand-in loads there (base 0, in bounds) and its own clamped loads after.
+    auto step = [&](RwStage<KTW, WQ>& sc, const RwItem<KTW>& cu, RwStage<KTW, WQ>& sn, const RwItem<KTW>& nx) {
+        if (cu.edge || !full) fix(sc, cu);  // (an interior item has nothing to fix)
+        constexpr int KM = KTW / 2;  // the middle row goes first, with the loads (the rows' chains are apart)
+        f32x4 ca;
+        // (the fence and the scheduling barrier emit nothing; they keep the compiler from sinking
+        // the loads below the MFMAs, towards the step that uses them, which would undo the prefetch)
+        if (cu.rok[KM]) {
+            load_in(sn, nx);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_sched_barrier(0);
+            ca = grad(sc);
+            taps(sc, ca, KM);
+        } else {  // a kt row outside the input contributes zero
+            load_in(sn, nx);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_sched_barrier(0);
+            ca = grad(sc);
+        }
+#pragma unroll
+        for (int k = 0; k < KTW; ++k)
+            if (k != KM && cu.rok[k]) taps(sc, ca, k);
+        if (nx.ends) load_any(sn, nx);  // (load_in read a stand-in)
+    };
+    // two register stages, alternating: item it + NW is in flight while item it computes.
+    // The prefetches are unconditional (past the end they re-load the wave's last item and are
+    // never used).
     RwStage<KTW, WQ> s0, s1;
     const int it0 = it_beg + wv;
-    if (it0 < it_end) load(s0, it0);
-    for (int it = it0; it < it_end; it += 2 * NW) {
-        load(s1, min(it + NW, it_end - 1));
-        compute(s0);
-        if (it + NW >= it_end) break;
-        load(s0, min(it + 2 * NW, it_end - 1));
-        compute(s1);
+    if (it0 < it_end) {
+        RwPos pos;  // the only divisions: once per wave
+        const int r1 = it0 / a.SW, r2 = r1 / g.T2;
+        pos.cs = it0 - r1 * a.SW;
+        pos.t = r1 - r2 * g.T2;
+        pos.b = r2 / a.NCS;
+        pos.strip = r2 - pos.b * a.NCS;
+        RwItem<KTW> i0 = item(pos), i1;
+        load_any(s0, i0);
+        for (int it = it0;; it += 2 * NW) {
+            if (it + NW < it_end) advance(pos);
+            i1 = item(pos);
+            step(s0, i0, s1, i1);
+            if (it + NW >= it_end) break;
+            if (it + 2 * NW < it_end) advance(pos);
+            i0 = item(pos);
+            step(s1, i1, s0, i0);
+            if (it + 2 * NW >= it_end) break;
+        }
     }
     if constexpr (NW > 1) {
         // ---- fixed-order workgroup sum through LDS, then one contiguous task partial
