@@ -149,6 +149,16 @@ class CustomAudioDataset:
         n = len(self.pool)
         return self.fixed_length if self.fixed_length and n > self.fixed_length else n
 
+    def get(self, idx: tp.Optional[int] = None) -> torch.Tensor:
+        """customAudioDataset.py:31-55: clip `idx` uncropped and untransformed, [channels][T] (a
+        mono clip expanded); a random.randrange(len(self)) pick when idx is None."""
+        if idx is None:
+            idx = random.randrange(len(self))
+        if not 0 <= idx < len(self.pool):
+            raise IndexError(f'clip {idx} of {len(self.pool)}')
+        L = int(self.pool.lengths[idx])
+        return self.pool.gather([idx], [0], [L], self.channels)[0]
+
     def _window(self, i):
         L = int(self.pool.lengths[i])
         if self.tensor_cut > 0 and L > self.tensor_cut:
@@ -156,14 +166,15 @@ class CustomAudioDataset:
             return start, self.tensor_cut
         return 0, L
 
-    def make_batch(self, indices: tp.Sequence[int]) -> torch.Tensor:
+    def make_batch(self, indices: tp.Sequence[int], return_lengths: bool = False):
         """[dataset[i] for i in indices] + collate_fn (customAudioDataset.py:58-91) as one
-        launch; crop starts drawn in item order like the reference's DataLoader does."""
+        launch; crop starts drawn in item order like the reference's DataLoader does. With
+        return_lengths also the items' lengths before the zero pad (a list)."""
         wins = [self._window(int(i)) for i in indices]
         out = self.pool.gather(indices, [w[0] for w in wins], [w[1] for w in wins], self.channels)
         if self.transform is not None:
             out = self.transform(out)
-        return out
+        return (out, [w[1] for w in wins]) if return_lengths else out
 
     def batches(self, batch_size: int, shuffle: bool = True, drop_last: bool = True):
         """DataLoader(shuffle) order over __len__ (train_multi_gpu.py:277-282)."""

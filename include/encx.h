@@ -566,6 +566,30 @@ int encx_resample_table(float* host_table, int64_t orig, int64_t neu);
 int encx_resample(const float* x, const float* table, float* y, int64_t B, int64_t Cin, int64_t Cout, int64_t L,
                   int64_t orig, int64_t neu, encx_stream_t stream);
 
+/* ------------------------------------------------------ STOI (cal_metrics.py:57-63)
+ * Short-time objective intelligibility (Taal, Hendriks, Heusdens, Jensen 2011; extended=False)
+ * of degraded rows y against clean rows x, both [B][T] at 10 kHz, one score per row into out [B].
+ * lengths (int64 [B] on the device, nullable = T for every row) gives each row's samples,
+ * clamped to [0, T]. With NF 256, HOP 128, w = hanning(258)[1:-1], EPS = 2^-52 a row of len
+ * samples has F = encx_stoi_frames(len) = ceil((len - NF) / HOP) frames (0 for len <= NF; the
+ * frame that would end exactly at len is not taken); the frames of x within 40 dB of its
+ * loudest, 20 log10(||w x_i|| + EPS), are kept and the kept windowed frames of x and of y are
+ * overlap-added at spacing HOP; the n - 1 frames of those signals (n = frames kept), windowed
+ * again, go through a 512-point real FFT, and the square roots of the power summed over the 15
+ * third-octave bands from 150 Hz (bins [7, 9) .. [174, 219)) are correlated over every run of 30
+ * frames after scaling y's run to x's norm and clipping it at (1 + 10^(15/20)) x; the score is
+ * the mean over runs and bands, or 1e-5 for fewer than 30 such frames (the published
+ * implementation's warning value, which cal_metrics.py:132 filters out).
+ * ws: encx_stoi_workspace_floats(B, T) 4-byte words, 8-byte aligned; on return its first B words
+ * hold each row's kept count n as int32. T <= 2^22; a longer row, a negative size or a null
+ * pointer is ENCX_EINVAL (-1 from the two queries). Five launches and no host synchronisation:
+ * n stays on the device and grids are sized from encx_stoi_frames(T). Every sum runs in a fixed
+ * order, so a row's bits depend neither on the batch around it nor on T beyond its own length. */
+int64_t encx_stoi_frames(int64_t len);
+int64_t encx_stoi_workspace_floats(int64_t B, int64_t T);
+int encx_stoi(const float* x, const float* y, const int64_t* lengths, float* ws, float* out, int64_t B, int64_t T,
+              encx_stream_t stream);
+
 /* ------------------------------------------------------ LM entropy coding (use_lm=True)
  * LMModel (model.py:27-65) over StreamingTransformerEncoder (modules/transformer.py:62-119),
  * inference only, and the arithmetic coder of quantization/ac.py. Activations are [B][T][D]
