@@ -1,5 +1,5 @@
-"""The register-window weight grad of the strided Conv2d (c2_wgrad_rw_kernel, csrc/disc.hip), at
-the smallest shapes that reach each of its paths: interior items (no fix-up, loads at a scalar
+"""The register-window weight grad of the strided Conv2d (c2_wgrad_rw_kernel,
+csrc/conv2d_wgrad.hip), at the smallest shapes that reach each of its paths: interior items (no fix-up, loads at a scalar
 base), row-edge chunks, kt rows outside the input, partial channel tiles, the tensor's first and
 last quads, odd tails of the two-stage item loop and splits with fewer items than waves; with and
 without the LeakyReLU' mask, in the 8-wave workgroup form and the one-wave form. Weight and bias

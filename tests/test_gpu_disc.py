@@ -1,5 +1,5 @@
-"""GPU parity of the MS-STFT discriminator path (csrc/disc.hip through the C ABI): the G5
-fixture generated from the reference, the fp64 oracle at 1 s clips (forward, input grad,
+"""GPU parity of the MS-STFT discriminator path (csrc/disc.hip and csrc/conv2d_*.hip through the
+C ABI): the G5 fixture generated from the reference, the fp64 oracle at 1 s clips (forward, input grad,
 weight grads), the adversarial / feature / discriminator losses, and the GAN train step."""
 import numpy as np
 import pytest
@@ -195,7 +195,9 @@ LAYERS = [(2, 32, (3, 9), (1, 1), (1, 1), (1, 4)),
           (32, 32, (3, 3), (1, 1), (1, 1), (1, 1)),
           (32, 1, (3, 3), (1, 1), (1, 1), (1, 1)),
           (4, 32, (3, 9), (1, 1), (1, 1), (1, 4)),  # first layer of the 48 kHz stereo disc
-          (32, 1, (3, 3), (1, 2), (2, 1), (2, 1))]  # one output channel, strided + dilated (+ act)
+          (32, 1, (3, 3), (1, 2), (2, 1), (2, 1)),  # one output channel, strided + dilated (+ act)
+          (64, 64, (3, 9), (1, 2), (1, 1), (1, 4)),  # filters=64: the 64-row tiled kernels and the
+          (64, 64, (3, 3), (1, 1), (1, 1), (1, 1))]  # generic weight grad with two row tiles
 
 
 @pytest.fixture(params=[0, 1, 2], ids=['auto', 'regwin', 'tiled'])

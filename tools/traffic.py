@@ -16,7 +16,7 @@ import csv
 import json
 import re
 
-# kernels launched by the conv / convtr / conv2d ABI entry points (csrc/conv1d.hip, disc.hip)
+# kernels launched by the conv / convtr / conv2d ABI entry points (csrc/conv1d.hip, conv2d_*.hip)
 # (csrc/resblock.hip's fused residual-block kernels are conv ABI calls too: encx_resblock_*)
 # (round 6: the v2 kernels, and the short-T layers' im2col / epilogue kernels with their hipBLASLt
 # GEMMs, `Cijk_*`; the LSTM weight grads' library GEMMs carry the same names and are counted in
