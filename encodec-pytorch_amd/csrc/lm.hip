@@ -1,5 +1,6 @@
 // encx -- the entropy-coding language model (model.py:27-65 LMModel over
-// modules/transformer.py:62-119 StreamingTransformerEncoder), inference only.
+// modules/transformer.py:62-119 StreamingTransformerEncoder); its training backward
+// is csrc/lm_train.hip.
 //
 // One code path serves both directions of the LM entropy coder (compress.py:74-89 /
 // 129-155): the encoder knows every code up front and runs all T steps of a frame as ONE pass

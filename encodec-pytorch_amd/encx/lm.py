@@ -13,6 +13,10 @@ batch of equal-shape frames: the encoder runs all T steps of a frame as one pass
 is known), the decoder one step per launch sequence; csrc/lm.hip computes every row in a
 fixed order that does not depend on the rows sharing the launch, so both sides produce the
 same cdfs bit for bit.
+
+`nll(codes)` trains the LM (csrc/lm_train.hip): the teacher-forced forward is the encoder's own
+pass, so the loss is the log-probability the arithmetic coder will see, and one autograd Function
+runs the hand-written backward and hands every parameter its gradient.
 """
 import typing as tp
 
@@ -81,6 +85,129 @@ class LMState:
                 self.kv[i] = nkv
 
 
+class _NLLFn(torch.autograd.Function):
+    """LMModel.nll: the coding forward with every layer's workspace and cache kept, the fused
+    cross-entropy + gradient and the heads backward chunk by chunk in the forward (the logits
+    never exist whole), the layers and the input stage in the backward."""
+
+    @staticmethod
+    def forward(ctx, lm, codes, chunk_floats, *params):
+        tr = lm.transformer
+        B, K, T = codes.shape
+        N, D, Fh, card = B * T, lm.dim, tr.hidden, lm.card
+        dev = codes.device
+        st = stream()
+        f32 = lambda nbytes: torch.empty((int(nbytes) + 3) // 4, device=dev)
+        need = any(ctx.needs_input_grad)  # False under no_grad: the loss alone
+        sb, sk, s_t = codes.stride()
+        state = lm.new_state(B, T + 1)
+        x = torch.empty(N, D, device=dev)
+        call('encx_lm_input', codes.data_ptr(), sb, sk, s_t, B, K, T, 1, lm._emb.data_ptr(), card + 1, D,
+             tr.norm_in.weight.data_ptr(), tr.norm_in.bias.data_ptr(), 0, None, float(tr.max_period),
+             x.data_ptr(), st)
+        xs, works = [x], []
+        for i, layer in enumerate(tr.layers):
+            if need or not works:
+                works.append(f32(lib.encx_lm_layer_workspace(N, D, Fh)))
+            y = torch.empty_like(x)
+            call('encx_lm_layer', x.data_ptr(), y.data_ptr(), B, T, state.kv[i].data_ptr(), state.capacity, 1, None,
+                 tr.past_context, D, tr.num_heads, Fh, *_layer_ptrs(layer), works[-1].data_ptr(), st)
+            xs.append(y)
+            x = y
+        # heads, loss and dlogits, heads backward: row chunks of whole rows
+        rows = max(1, min(N, chunk_floats // (K * card)))
+        logits = f32(lib.encx_lm_heads_workspace(rows, K, card))
+        probas = torch.empty(rows * K * card, device=dev)
+        ce = f32(lib.encx_lm_ce_workspace(N, K))
+        scale = 1.0 / (N * K)
+        if need:
+            hw = f32(lib.encx_lm_heads_bwd_workspace(rows, D, K, card))
+            dx = torch.empty(N, D, device=dev)
+            g_w = torch.zeros(lm.n_q, card, D, device=dev) if K < lm.n_q else torch.empty(K, card, D, device=dev)
+            g_b = torch.zeros(lm.n_q, card, device=dev) if K < lm.n_q else torch.empty(K, card, device=dev)
+        for n0 in range(0, N, rows):
+            r = min(rows, N - n0)
+            xc = x.data_ptr() + n0 * D * 4
+            call('encx_lm_heads', xc, 1, r, D, lm._lin_w.data_ptr(), lm._lin_b.data_ptr(), K, card,
+                 logits.data_ptr(), probas.data_ptr(), None, TOTAL_RANGE_BITS, ROUNDOFF, MIN_RANGE, None, 0, 0, 0,
+                 None, None, st)
+            call('encx_lm_ce', logits.data_ptr(), n0, r, N, T, K, card, codes.data_ptr(), sb, sk, s_t, scale,
+                 ce.data_ptr(), st)
+            if need:
+                call('encx_lm_heads_bwd', logits.data_ptr(), xc, r, D, lm._lin_w.data_ptr(), K, card,
+                     dx.data_ptr() + n0 * D * 4, g_w.data_ptr(), g_b.data_ptr(), int(n0 > 0), hw.data_ptr(), st)
+        out = torch.empty((), device=dev)
+        # codes were range-checked before the first launch (LMModel.nll): the count is not read
+        err = torch.empty(1, device=dev, dtype=torch.int32)
+        call('encx_lm_ce_finish', ce.data_ptr(), N, K, scale, out.data_ptr(), err.data_ptr(), st)
+        if need:
+            ctx.lm, ctx.codes, ctx.xs, ctx.works, ctx.kv = lm, codes, xs, works, state.kv
+            ctx.emb = lm._emb  # the stack this forward read (an optimiser step may follow)
+            ctx.head_grads = (dx, g_w, g_b)
+            # the backward reads the layers' live parameters (nothing is copied): see backward
+            ctx.versions = [(p.data_ptr(), p._version) for p in params]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lm, codes = ctx.lm, ctx.codes
+        if ctx.head_grads is None:
+            raise RuntimeError('encx LM: nll can be differentiated once (its saved activations are released by '
+                               'the first backward; retain_graph is not supported): call nll again')
+        if ctx.versions != [(p.data_ptr(), p._version) for p in lm._train_params()]:
+            raise RuntimeError('encx LM: a parameter changed between nll() and backward(); the backward reads the '
+                               'live parameters, so run backward before the optimiser step')
+        tr = lm.transformer
+        B, K, T = codes.shape
+        N, D, Fh, card = B * T, lm.dim, tr.hidden, lm.card
+        dev = codes.device
+        st = stream()
+        f32 = lambda nbytes: torch.empty((int(nbytes) + 3) // 4, device=dev)
+        dy, g_w, g_b = ctx.head_grads
+        # the loss's own scale 1 / (N K) is inside the kernels; the incoming grad multiplies on top.
+        # Everything below is linear in the heads' three results, so scaling them scales every grad.
+        dy, g_w, g_b = dy * g, g_w * g, g_b * g
+        work = f32(lib.encx_lm_layer_bwd_workspace(B, T, D, tr.num_heads, Fh))
+        layer_grads = []
+        for i in reversed(range(len(tr.layers))):
+            layer = tr.layers[i]
+            a = layer.self_attn
+            ps = [a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias, layer.linear1.weight,
+                  layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, layer.norm1.weight,
+                  layer.norm1.bias, layer.norm2.weight, layer.norm2.bias]
+            gs = [torch.empty_like(p) for p in ps]
+            dx = torch.empty(N, D, device=dev)
+            call('encx_lm_layer_bwd', dy.data_ptr(), dx.data_ptr(), ctx.xs[i].data_ptr(), B, T, ctx.kv[i].data_ptr(),
+                 ctx.kv[i].shape[1], tr.past_context, D, tr.num_heads, Fh, a.in_proj_weight.data_ptr(),
+                 a.in_proj_bias.data_ptr(), a.out_proj.weight.data_ptr(), layer.linear1.weight.data_ptr(),
+                 layer.linear1.bias.data_ptr(), layer.linear2.weight.data_ptr(), layer.norm1.weight.data_ptr(),
+                 layer.norm2.weight.data_ptr(), ctx.works[i].data_ptr(), *[t.data_ptr() for t in gs],
+                 work.data_ptr(), st)
+            layer_grads.append(gs)
+            dy = dx
+        g_nw, g_nb = torch.empty(D, device=dev), torch.empty(D, device=dev)
+        g_emb = torch.zeros(lm.n_q, card + 1, D, device=dev) if K < lm.n_q \
+            else torch.empty(K, card + 1, D, device=dev)
+        sb, sk, s_t = codes.stride()
+        iw = f32(lib.encx_lm_input_bwd_workspace(B, T, D, K))
+        call('encx_lm_input_bwd', dy.data_ptr(), codes.data_ptr(), sb, sk, s_t, B, K, T, ctx.emb.data_ptr(), card + 1,
+             D, tr.norm_in.weight.data_ptr(), g_emb.data_ptr(), g_nw.data_ptr(), g_nb.data_ptr(), iw.data_ptr(), st)
+        grads = [g_nw, g_nb]
+        for gs in reversed(layer_grads):
+            grads += gs
+        grads += list(g_emb.unbind(0)) + list(g_w.unbind(0)) + list(g_b.unbind(0))
+        ctx.xs = ctx.works = ctx.kv = ctx.head_grads = None
+        return (None, None, None, *grads)
+
+
+def _layer_ptrs(layer):
+    a = layer.self_attn
+    return [t.data_ptr() for t in (a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
+                                   layer.linear1.weight, layer.linear1.bias, layer.linear2.weight,
+                                   layer.linear2.bias, layer.norm1.weight, layer.norm1.bias, layer.norm2.weight,
+                                   layer.norm2.bias)]
+
+
 class LMModel(nn.Module):
     """model.py:27-45."""
 
@@ -95,9 +222,17 @@ class LMModel(nn.Module):
         self._packed_key = None
 
     # ------------------------------------------------------------------ weights
+    def invalidate_packed(self):
+        """Forget the stacked copies of the embeddings and heads: the next call restacks them.
+        The cache key below (data_ptr, _version) cannot see an optimiser that writes through raw
+        pointers (FlatAdam / encx_adam_step), so `nll` restacks on every call and leaves the
+        cache invalid behind it; call this after such a step taken without an `nll` since the
+        last use of the model."""
+        self._packed_key = None
+
     def _packed(self):
         """The K embedding tables and output heads stacked into contiguous [n_q][.][dim]
-        buffers (rebuilt only when a parameter changes)."""
+        buffers (rebuilt only when a parameter changes, see invalidate_packed)."""
         ps = [e.weight for e in self.emb] + [l.weight for l in self.linears] + [l.bias for l in self.linears]
         key = tuple((p.data_ptr(), p._version) for p in ps)
         if key != self._packed_key:
@@ -164,6 +299,48 @@ class LMModel(nn.Module):
              sym.data_ptr() if sym is not None else None, s[0], s[1], s[2],
              lohi.data_ptr() if lohi is not None else None, err.data_ptr() if err is not None else None,
              stream())
+
+    # ------------------------------------------------------------------ training
+    def _train_params(self):
+        """Parameters in the order _NLLFn takes and returns them."""
+        tr = self.transformer
+        ps = [tr.norm_in.weight, tr.norm_in.bias]
+        for layer in tr.layers:
+            a = layer.self_attn
+            ps += [a.in_proj_weight, a.in_proj_bias, a.out_proj.weight, a.out_proj.bias,
+                   layer.linear1.weight, layer.linear1.bias, layer.linear2.weight, layer.linear2.bias,
+                   layer.norm1.weight, layer.norm1.bias, layer.norm2.weight, layer.norm2.bias]
+        ps += [e.weight for e in self.emb] + [l.weight for l in self.linears] + [l.bias for l in self.linears]
+        return ps
+
+    def nll(self, codes: torch.Tensor, chunk_floats: int = 1 << 25) -> torch.Tensor:
+        """Mean negative log-likelihood (nats per code) of codes int64 [B, K, T] under the
+        teacher-forced LM: exactly the probabilities `encode_streams` codes them with.
+        Differentiable with respect to every parameter; heads and embeddings k >= K get zero
+        gradients. The heads run in row chunks of at most `chunk_floats` logits.
+
+        Limits: the backward reads the live parameters, so it must run before anything changes
+        them (an in-place change is refused; a write through raw pointers, as FlatAdam's step
+        makes, cannot be seen and gives wrong layer gradients); and the loss can be
+        differentiated once (no retain_graph: the saved activations are released)."""
+        self.invalidate_packed()
+        self._packed()
+        self.invalidate_packed()  # an optimiser step follows: never trust this stack again
+        self._check_device()
+        if codes.dtype != torch.int64 or codes.dim() != 3 or not codes.is_cuda:
+            raise RuntimeError('encx LM: codes must be int64 [B, K, T] on the GPU')
+        if codes.device != self._emb.device:
+            raise RuntimeError(f'encx LM: codes on {codes.device}, parameters on {self._emb.device}')
+        B, K, T = codes.shape
+        if K > self.n_q:
+            raise ValueError(f'{K} codebooks for an LM of n_q={self.n_q}')
+        if B < 1 or T < 1:
+            raise ValueError('encx LM: nll needs at least one code')
+        # the input stage reads the embedding table at the code: check before any launch
+        lo, hi = codes.aminmax()
+        if int(lo) < 0 or int(hi) >= self.card:
+            raise ValueError(f'a code is outside [0, {self.card})')
+        return _NLLFn.apply(self, codes, int(chunk_floats), *self._train_params())
 
     @torch.no_grad()
     def forward(self, indices: torch.Tensor, states: tp.Optional[LMState] = None, offset: int = 0):

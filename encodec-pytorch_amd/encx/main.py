@@ -12,6 +12,8 @@ Differences from the reference, by design:
     torchaudio) and brought to the model's rate and channels on the GPU (encx.utils.convert_audio);
   * the reference's decode branch cannot run (main.py:97 passes no model and calls
     `args.device()`); here it does what it means to: decompress(model, bytes, device=args.device);
+  * a checkpoint that carries an LM trained by encx/train_lm.py ('lm_state_dict', written by
+    its --merge-into) codes with that LM under -l;
   * pretrained weights are remote-only, so `encodec_24khz` / `encodec_48khz` take theirs from
     `-c FILE` (a state dict, or a checkpoint holding `model_state_dict`), loaded with
     weights_only=True, and stop with a message without it.
@@ -123,11 +125,12 @@ def load_weights(model_name, checkpoint):
     if not os.path.exists(checkpoint):
         fatal(f"Checkpoint {checkpoint} does not exist.")
     model = MODELS[model_name](pretrained=False)
-    sd = torch.load(checkpoint, map_location='cpu', weights_only=True)
+    ckpt = sd = torch.load(checkpoint, map_location='cpu', weights_only=True)
     if isinstance(sd, dict) and 'model_state_dict' in sd:
         sd = sd['model_state_dict']
     model.load_state_dict(sd)
     model.name = model_name
+    model.install_lm(ckpt)  # an LM trained by encx/train_lm.py and merged into the file
     return model.eval()
 
 

@@ -149,6 +149,25 @@ class EncodecModel(nn.Module):
         """Use `lm` (an encx.lm.LMModel) for use_lm=True instead of the pretrained one."""
         self._lm_model = lm
 
+    def install_lm(self, ckpt) -> bool:
+        """A checkpoint written by encx/train_lm.py (--merge-into) carries the entropy-coding LM
+        trained for this codec as 'lm_state_dict' + 'lm_config' (LMModel's constructor
+        arguments): build it and install it with set_lm_model. Files without the key are left
+        as they are (-> False).
+
+        set_lm_model keeps the LM as a submodule (which is how `.to(device)` moves it along), so
+        a codec with an LM installed lists `_lm_model.*` in state_dict() and parameters(): save
+        such a codec with `{k: v for k, v in state_dict().items() if not k.startswith('_lm_model.')}`
+        as its 'model_state_dict' (a fresh EncodecModel refuses the extra keys), and the LM under
+        'lm_state_dict' / 'lm_config' as train_lm.py does."""
+        if not isinstance(ckpt, dict) or 'lm_state_dict' not in ckpt:
+            return False
+        from .lm import LMModel
+        lm = LMModel(**ckpt['lm_config'])
+        lm.load_state_dict(ckpt['lm_state_dict'])
+        self.set_lm_model(lm.eval())
+        return True
+
     def get_lm_model(self):
         """model.py:221-240: LMModel(n_q, bins, num_layers=5, dim=200, past_context=3.5 s of
         frames) with the pretrained weights of this model."""
@@ -211,9 +230,11 @@ class EncodecModel(nn.Module):
         'quantizer.model' prefix renamed. Loaded with weights_only=True (no unpickling)."""
         import os
         assert os.path.exists(checkpoint), "checkpoint not exists"
-        pre_dic = torch.load(checkpoint, map_location='cpu', weights_only=True)['model_state_dict']
+        ckpt = torch.load(checkpoint, map_location='cpu', weights_only=True)
+        pre_dic = ckpt['model_state_dict']
         model.load_state_dict({k.replace('quantizer.model', 'quantizer.vq'): v for k, v in pre_dic.items()})
         model.eval()
+        model.install_lm(ckpt)
         return model
 
     @staticmethod

@@ -591,12 +591,12 @@ int encx_stoi(const float* x, const float* y, const int64_t* lengths, float* ws,
               encx_stream_t stream);
 
 /* ------------------------------------------------------ LM entropy coding (use_lm=True)
- * LMModel (model.py:27-65) over StreamingTransformerEncoder (modules/transformer.py:62-119),
- * inference only, and the arithmetic coder of quantization/ac.py. Activations are [B][T][D]
- * fp32 (row n = b*T + t). Every kernel computes a row from that row's inputs alone in a fixed
- * reduction order, so a row's bits do not depend on how many rows share a launch: the encoder
- * runs a frame's T steps as one pass, the decoder one step at a time, and both see identical
- * cdfs (the precondition of arithmetic decoding, ac.py:220-224).
+ * LMModel (model.py:27-65) over StreamingTransformerEncoder (modules/transformer.py:62-119)
+ * and the arithmetic coder of quantization/ac.py (training: the section after this one).
+ * Activations are [B][T][D] fp32 (row n = b*T + t). Every kernel computes a row from that row's
+ * inputs alone in a fixed reduction order, so a row's bits do not depend on how many rows share a
+ * launch: the encoder runs a frame's T steps as one pass, the decoder one step at a time, and
+ * both see identical cdfs (the precondition of arithmetic decoding, ac.py:220-224).
  *
  * encx_lm_input: the LM input (model.py:59-60: sum_k emb[k][idx], k in order), norm_in
  * LayerNorm and the sin position embedding of step offset + t (transformer.py:16-27, 104-113).
@@ -670,6 +670,57 @@ int encx_ac_decode(const uint8_t* data, int64_t stride, const int64_t* nbytes, i
  * (nullable) to their offset / seq0 / t, so one captured decode step (a hipGraph) replays for
  * every step; the caller guarantees seq0 + *dev_step + T <= L. */
 int encx_lm_step_advance(int64_t* dev_step, int64_t by, encx_stream_t stream);
+
+/* ------------------------------------------------------ LM training (teacher-forced, one GPU)
+ * The training forward is the coding forward above, unchanged (encx_lm_input shifted = 1,
+ * encx_lm_layer at seq0 = 1 on a fresh cache, encx_lm_heads), each layer keeping its own
+ * encx_lm_layer workspace (q, ctx, h1, x1, ff, h2) and k | v cache until its backward. The
+ * linear1 pre-activation, the LayerNorm statistics and the attention's softmax rows are recomputed
+ * here. Every reduction runs in a fixed order without atomics (split-K slabs summed by a second
+ * pass, one owner per key position and per embedding row): two runs give identical bits. Grad
+ * outputs are overwritten unless said otherwise; nothing is allocated; work sizes in bytes come
+ * from the *_workspace queries (-1 for sizes out of range).
+ *
+ * encx_lm_ce: rows [n0, n0 + rows) of the N = B*T rows, whose heads' logits [rows][K][card]
+ * (encx_lm_heads' work buffer) become (softmax - onehot(code)) * scale in place; -log p[code] of
+ * every (row, k) goes to work (encx_lm_ce_workspace(N, K) bytes, shared by the chunks of one
+ * pass). A code sym[b*s_b + k*s_k + t*s_t] outside [0, card) zeroes its gradient row and is
+ * counted. encx_lm_ce_finish: *loss = scale * the sum over all N*K entries, *err = that count. */
+int64_t encx_lm_ce_workspace(int64_t N, int64_t K);
+int encx_lm_ce(float* logits, int64_t n0, int64_t rows, int64_t N, int64_t T, int64_t K, int64_t card,
+               const int64_t* sym, int64_t s_b, int64_t s_k, int64_t s_t, float scale, float* work,
+               encx_stream_t stream);
+int encx_lm_ce_finish(const float* work, int64_t N, int64_t K, float scale, float* loss, int* err,
+                      encx_stream_t stream);
+/* Heads backward for N rows: dx [N][D] = dlogits w, dw [K*card][D] (+)= dlogits^T x and db
+ * [K*card] (+)= the column sums of dlogits ([N][K*card]); accumulate != 0 adds to dw / db (the
+ * later row chunks of one pass). w is the stacked [K][card][D] of encx_lm_heads.
+ * encx_lm_heads_bwd_workspace(N, ...) bytes suffice for every call with at most N rows (the
+ * query never shrinks as N grows), so one buffer sized for the largest chunk serves them all. */
+int64_t encx_lm_heads_bwd_workspace(int64_t N, int64_t D, int64_t K, int64_t card);
+int encx_lm_heads_bwd(const float* dlogits, const float* x, int64_t N, int64_t D, const float* w, int64_t K,
+                      int64_t card, float* dx, float* dw, float* db, int accumulate, float* work,
+                      encx_stream_t stream);
+/* Backward of encx_lm_layer(x -> y) at seq0 = 1: dy [B][T][D] -> dx, and the grads of its twelve
+ * parameters. x is the layer's input, kv / fwd_work the cache and workspace its forward filled.
+ * In order: norm2, linear2, linear1 (GELU' of the recomputed pre-activation), the residual join,
+ * norm1, out_proj, attention (dq; dk / dv per key position over the causal window), in_proj.
+ * Key position 0 is the phantom zero input whose k | v are the in_proj biases: its dk | dv are
+ * added to g_in_b[D:3D] on top of the rows' column sums. */
+int64_t encx_lm_layer_bwd_workspace(int64_t B, int64_t T, int64_t D, int64_t heads, int64_t F);
+int encx_lm_layer_bwd(const float* dy, float* dx, const float* x, int64_t B, int64_t T, const float* kv, int64_t L,
+                      int64_t past_context, int64_t D, int64_t heads, int64_t F, const float* in_w,
+                      const float* in_b, const float* out_w, const float* l1_w, const float* l1_b,
+                      const float* l2_w, const float* n1_w, const float* n2_w, const float* fwd_work, float* g_in_w,
+                      float* g_in_b, float* g_out_w, float* g_out_b, float* g_l1_w, float* g_l1_b, float* g_l2_w,
+                      float* g_l2_b, float* g_n1_w, float* g_n1_b, float* g_n2_w, float* g_n2_b, float* work,
+                      encx_stream_t stream);
+/* Backward of encx_lm_input(shifted = 1): dx [B][T][D] -> the norm_in grads and g_emb
+ * [K][card1][D], every row written (zero where no input used it; row 0 is the t = 0 token). */
+int64_t encx_lm_input_bwd_workspace(int64_t B, int64_t T, int64_t D, int64_t K);
+int encx_lm_input_bwd(const float* dx, const int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t, int64_t B,
+                      int64_t K, int64_t T, const float* emb, int64_t card1, int64_t D, const float* ln_w,
+                      float* g_emb, float* g_ln_w, float* g_ln_b, float* work, encx_stream_t stream);
 
 #ifdef __cplusplus
 }
