@@ -722,6 +722,55 @@ int encx_lm_input_bwd(const float* dx, const int64_t* codes, int64_t s_b, int64_
                       int64_t K, int64_t T, const float* emb, int64_t card1, int64_t D, const float* ln_w,
                       float* g_emb, float* g_ln_w, float* g_ln_b, float* work, encx_stream_t stream);
 
+/* ---------------------------------------------------------------- streaming codec (encx/streaming.py)
+ * Stateful chunked forward of the CAUSAL SEANet: a step delivers n latent frames per stream. Every
+ * tensor between two layers lives in a caller-owned WINDOW [B][C][P + columns]: the first P columns
+ * are the history carried from the previous step (pre-activation), the step's columns follow.
+ * Windows and outputs are addressed with explicit element strides (b: one batch item, r: one
+ * channel row), so a layer writes straight behind its consumer's history. Inference only.
+ * Determinism: an output element's reduction order depends on the layer alone (Cin, K), never on
+ * B, on the number of columns, or on the column's place in a tile: results are bit-identical
+ * however the audio is sliced into steps and whichever streams share the batch.
+ *
+ * Valid (unpadded) Conv1d over a window. `win` points at the first column the conv reads (the
+ * layer's own P = (K-1)*dilation - (stride-1) history columns before the chunk):
+ * y[b,co,t] = bias[co] + sum_{ci,k} W[co,ci,k] act(win[b,ci,t*stride + k*dilation]) (+ y[b,co,t]
+ * when add_into_y: the residual, already in place), t < n_out. wf as encx_weightnorm_fwd writes it
+ * ([Cin][K][Cout]); bias may be NULL. */
+int encx_stream_conv1d(const float* win, const float* wf, const float* bias, float* y, int64_t B, int64_t Cin,
+                       int64_t Cout, int64_t n_out, int64_t K, int64_t stride, int64_t dilation,
+                       int64_t win_bstride, int64_t win_rstride, int64_t y_bstride, int64_t y_rstride, int pre_act,
+                       int add_into_y, encx_stream_t stream);
+/* Causal ConvTranspose1d with K = 2*stride over the window [prev | chunk] (`win` points at prev,
+ * n_in chunk columns follow): the n_in*stride finished samples
+ * y[b,co,i*stride+r] = bias[co] + sum_ci Wt[ci,co,r] act(win[b,ci,i+1]) + Wt[ci,co,r+stride] act(win[b,ci,i]).
+ * wp as encx_weightnorm_fwd writes it for (A0 = Cin, A1 = Cout, K, stride). A stream's first chunk
+ * has prev = 0. */
+int encx_stream_convtr1d(const float* win, const float* wp, const float* bias, float* y, int64_t B, int64_t Cin,
+                         int64_t Cout, int64_t n_in, int64_t stride, int64_t win_bstride, int64_t win_rstride,
+                         int64_t y_bstride, int64_t y_rstride, int pre_act, encx_stream_t stream);
+/* n steps of all L LSTM layers from the carried state, written back in place: hz [L][B][2H] is
+ * each layer's step input [x | h] (its second half is the carried h), c [L][B][H] the cell.
+ * x [B][H][>= n] and out (= h of the last layer, + x when skip) are strided like windows; gates:
+ * workspace of B*4H floats. wcatT, bsum from encx_lstm_pack. Nothing is saved for a backward.
+ * 1 + 2L launches per step; the launch boundary is the only grid-wide dependency. B <= 64,
+ * H % 16 == 0, H <= 1024. */
+int encx_stream_lstm(const float* x, const float* wcatT, const float* bsum, float* hz, float* c, float* gates,
+                     float* out, int skip, int64_t B, int64_t n, int64_t H, int64_t L, int64_t x_bstride,
+                     int64_t x_rstride, int64_t out_bstride, int64_t out_rstride, encx_stream_t stream);
+/* End of a step, ONE launch for every window of a device table: row i of window w (rows = B*C
+ * rows of rstride floats from ptr; row0 = first row of the window in the concatenation,
+ * ascending; rows_total = their sum) moves its columns [n_cols, n_cols + P) to [0, P). The ranges
+ * overlap when n_cols < P: a row is loaded whole before any store. reflect != 0 (a stream's first
+ * chunk, before the window's consumer runs) writes column c <- column 2P - c instead, the
+ * reflect padding of pad1d (needs n_cols > P). P <= 64. */
+typedef struct {
+    float* ptr;
+    int64_t rows, P, n_cols, rstride, row0;
+} encx_stream_win;
+int encx_stream_roll(const encx_stream_win* wins, int64_t n_wins, int64_t rows_total, int reflect,
+                     encx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,129 @@
+"""Streaming codec step time: encx.streaming.StreamEncoder.encode / StreamDecoder.decode for B
+live streams advancing n latent frames per step (n * 320 samples each at 24 kHz), eager and as
+the replayed HIP graph, at B in {1, 16, 64} and n in {1, 4}.
+
+For comparison the offline kernels on a chunk of the same shape: model.encoder on [B, 1, n * 320]
+and model.decoder on [B, 128, n] (plus the same RVQ calls). That is what the existing kernels
+cost at this size; its result is NOT the stream's (every layer pads the chunk's own edges).
+
+The model is the causal 24 kHz architecture with its default random initialisation and random
+codebooks (nothing is read from outside the repository); the audio is seeded noise. A session is
+started with one first chunk of min_first_frames frames, then steps of n frames are timed: device
+events around blocks of steps, >= 0.3 s per variant, 5 rounds after a warm-up; median and the
+rounds' min / max. `real_time` is the one derived condition: at B = 64, n = 1 an encode step plus
+a decode step (graph replay) must take less than the frame period, 1000 / 75 = 13.33 ms.
+
+python tools/stream_bench.py [--batches 1,16,64] [--frames 1,4] [--rounds 5] [--out FILE]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, 'encodec-pytorch_amd'))
+
+BANDWIDTH = 6.0  # n_q = 8
+
+
+def stats(ms):
+    return {'ms': round(statistics.median(ms), 4), 'min': round(min(ms), 4), 'max': round(max(ms), 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batches', type=str, default='1,16,64')
+    ap.add_argument('--frames', type=str, default='1,4')
+    ap.add_argument('--rounds', type=int, default=5)
+    ap.add_argument('--min-seconds', type=float, default=0.3)
+    ap.add_argument('--out', type=str, default=os.path.join(ROOT, 'profiles', 'stream', 'stream_bench.json'))
+    args = ap.parse_args()
+    batches = [int(v) for v in args.batches.split(',')]
+    frames = [int(v) for v in args.frames.split(',')]
+
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit('stream_bench needs the GPU: nothing is measured without one')
+    from encx.model import EncodecModel
+    from encx.streaming import StreamEncoder, StreamDecoder
+    dev = torch.device('cuda:0')
+    torch.manual_seed(0)
+    m = EncodecModel.encodec_model_24khz()
+    for layer in m.quantizer.vq.layers:
+        layer._codebook.embed.normal_()
+        layer._codebook.inited.fill_(1.0)
+    m.set_target_bandwidth(BANDWIDTH)
+    m = m.to(dev)
+    hop, period_ms = int(m.encoder.hop_length), 1e3 / m.frame_rate
+
+    def timed(fn, iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    def measure(fn):
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        iters = max(5, int(args.min_seconds * 1e3 / args.rounds / max(timed(fn, 5), 1e-3)) + 1)
+        return stats([timed(fn, iters) for _ in range(args.rounds)]), iters
+
+    rows = []
+    with torch.no_grad():
+        for B in batches:
+            for n in frames:
+                g = torch.Generator().manual_seed(100 * B + n)
+                x = (0.1 * torch.randn(B, 1, n * hop, generator=g)).to(dev)
+                row = {'B': B, 'n': n, 'samples_per_step': n * hop}
+                for graphs in (False, True):
+                    enc = StreamEncoder(m, B, graphs=graphs)
+                    dec = StreamDecoder(m, B, enc.n_q, graphs=graphs)
+                    first = (0.1 * torch.randn(B, 1, enc.min_first_frames * hop, generator=g)).to(dev)
+                    dec.decode(enc.encode(first))
+                    codes = enc.encode(x)
+                    mode = 'graph' if graphs else 'eager'
+                    row[f'encode_{mode}'], it = measure(lambda: enc.encode(x))
+                    row[f'decode_{mode}'], _ = measure(lambda: dec.decode(codes))
+                    row[f'steps_per_round_{mode}'] = it
+                # the offline kernels on a chunk of the same shape (wrong edges: for the cost only)
+                embeds = [l._codebook.embed for l in m.quantizer.vq.layers[:enc.n_q]]
+                from encx import ops
+                cq = codes.permute(1, 0, 2).contiguous()
+                for key, fn in (('offline_encode_same_shape', lambda: ops.rvq_encode(m.encoder(x), embeds)),
+                                ('offline_decode_same_shape', lambda: m.decoder(ops.rvq_decode(cq, embeds)))):
+                    try:
+                        row[key], _ = measure(fn)
+                    except (RuntimeError, NotImplementedError) as e:
+                        if isinstance(e, RuntimeError) and 'code 9001' not in str(e):
+                            raise  # only a refused shape (ENCX_EINVAL) is a result; anything else ends the run
+                        row[key] = {'error': str(e)[:200]}
+                step = row['encode_graph']['ms'] + row['decode_graph']['ms']
+                row['encode_plus_decode_graph_ms'] = round(step, 4)
+                row['frame_periods_per_step'] = round(step / (n * period_ms), 4)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+
+    rt = [r for r in rows if r['B'] == 64 and r['n'] == 1]
+    res = {'metric': 'ms per streaming step (B streams x n latent frames), encode and decode',
+           'device': torch.cuda.get_device_name(0), 'model': 'causal 24 kHz SEANet, random weights, n_q 8',
+           'frame_period_ms': round(period_ms, 4), 'rounds': args.rounds,
+           'timing': f'device events around blocks of steps, >= {args.min_seconds} s per variant, after warm-up',
+           'rows': rows,
+           'real_time': None if not rt else {
+               'B': 64, 'n': 1, 'encode_plus_decode_graph_ms': rt[0]['encode_plus_decode_graph_ms'],
+               'frame_period_ms': round(period_ms, 4),
+               'met': rt[0]['encode_plus_decode_graph_ms'] < period_ms}}
+    print(json.dumps(res), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(json.dumps(res, indent=1) + '\n')
+
+
+if __name__ == '__main__':
+    main()
