@@ -27,6 +27,7 @@
 #include "prof.h"
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -181,23 +182,25 @@ __device__ int g_lstm_sync[(SYNC_LINES + 2) * SYNC_LINE];
 
 // Development tracing (build with -DENCX_LSTM_TRACE; encx_lstm_trace reads it): thread 0 of every
 // persistent workgroup stamps the steady clock at up to 8 points of every frame,
-// g_lstm_trace[kernel (0 fwd, 1 bwd)][workgroup < 256][frame < 128][point].
+// g_lstm_trace[kernel (0 fwd, 1 bwd)][workgroup < 256][frame < 128][point] (workgroup: the block
+// forward, the logical index (l, bg, s, nt) backward).
 #ifdef ENCX_LSTM_TRACE
 __device__ long long g_lstm_trace[2 * 256 * 128 * 8];
-#define LSTM_TRACE(kern, i, k)                                                               \
-    do {                                                                                     \
-        if (tid == 0 && blockIdx.x < 256 && (i) < 128)                                       \
-            g_lstm_trace[(((kern) * 256 + blockIdx.x) * 128 + (i)) * 8 + (k)] = wall_clock64(); \
+#define LSTM_TRACE(kern, wg, i, k)                                                      \
+    do {                                                                                \
+        if (tid == 0 && (wg) < 256 && (i) < 128)                                        \
+            g_lstm_trace[(((kern) * 256 + (wg)) * 128 + (i)) * 8 + (k)] = wall_clock64(); \
     } while (0)
 #else
-#define LSTM_TRACE(kern, i, k) \
-    do {                       \
+#define LSTM_TRACE(kern, wg, i, k) \
+    do {                           \
     } while (0)
 #endif
 
 // The persistent kernels' control word (host: pers_ctl): bits 0-4 log2 of the spin bound of every
-// poll (0: 20, about 1 s), bit 5 fault injection for tests: workgroup 0 never publishes, so its
-// consumers' polls time out (option LSTM_FAULT).
+// poll (0: 20, about 1 s), bit 5 fault injection for tests: one workgroup (the forward's first, the
+// backward's first recurrent one of layer 0) never publishes, so its consumers' polls time out
+// (option LSTM_FAULT).
 constexpr int CTL_FAULT = 32;
 ENCX_DEV int ctl_spins(int ctl) { return (ctl & 31) ? 1 << (ctl & 31) : 1 << 20; }
 // wave-wide bounded poll: cnt >= target (relaxed agent loads, sc1); false after `spins` tries
@@ -210,30 +213,39 @@ ENCX_DEV bool poll_ge(const int* cnt, int target, int* err, int spins) {
     return false;
 }
 // end of a persistent launch: the last workgroup to count itself done checks that every counter
-// line reached its final count (lines [0, n1) expect e1 arrivals, lines [n1, n1 + n2) expect e2; a
-// line off its count -- an arrival lost, or one left over from an earlier launch -- counts in the
-// error word), then zeroes the lines and the done count. Every workgroup has passed its last poll
-// before it counts itself, and the next launch on the stream starts after this one has ended.
+// line reached its final count (the lines are a list of consecutive ranges, each with the count
+// it expects; a line off its count -- an arrival lost, or one left over from an earlier launch --
+// counts in the error word), then zeroes the lines and the done count; its threads share the
+// lines, one each. Every workgroup has passed its last poll before it counts itself, and the next
+// launch on the stream starts after this one has ended.
 // Ordering: thread 0 made this workgroup's last arrivals; its s_waitcnt vmcnt(0) holds the done
 // arrival until those atomics have been performed, so the last workgroup's zeroing (issued after
-// its returning done add saw every other workgroup's) follows every arrival of the launch.
-ENCX_DEV void finish_launch(int* sync, int n1, int e1, int n2, int e2) {
+// its returning done add saw every other workgroup's, and a barrier) follows every arrival of the
+// launch.
+// (the ranges as scalars: an array of them indexed by the line's range went to scratch memory)
+struct SyncRange {
+    int n, e;  // n consecutive counter lines that each expect e arrivals
+};
+ENCX_DEV void finish_launch(int* sync, SyncRange r0, SyncRange r1 = {0, 0}, SyncRange r2 = {0, 0},
+                            SyncRange r3 = {0, 0}) {
+    __shared__ int s_last;
     __syncthreads();
+    int* done = sync + (SYNC_LINES + 1) * SYNC_LINE;
     if (threadIdx.x == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        int* done = sync + (SYNC_LINES + 1) * SYNC_LINE;
-        if (__hip_atomic_fetch_add(done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) {
-            int off = 0;
-            for (int i = 0; i < n1 + n2; ++i) {
-                const int v = __hip_atomic_load(sync + i * SYNC_LINE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                off += v != (i < n1 ? e1 : e2);
-            }
-            if (off) __hip_atomic_fetch_add(sync + SYNC_LINES * SYNC_LINE, off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (int i = 0; i < n1 + n2; ++i)
-                __hip_atomic_store(sync + i * SYNC_LINE, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(done, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        s_last = __hip_atomic_fetch_add(done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
     }
+    __syncthreads();
+    if (!s_last) return;
+    const int b1 = r0.n, b2 = b1 + r1.n, b3 = b2 + r2.n, total = b3 + r3.n;
+    int off = 0;
+    for (int i = threadIdx.x; i < total; i += blockDim.x) {
+        const int e = i < b1 ? r0.e : i < b2 ? r1.e : i < b3 ? r2.e : r3.e;
+        off += __hip_atomic_load(sync + i * SYNC_LINE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != e;
+        __hip_atomic_store(sync + i * SYNC_LINE, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (off) __hip_atomic_fetch_add(sync + SYNC_LINES * SYNC_LINE, off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x == 0) __hip_atomic_store(done, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 // the error word into a caller's running count, and cleared (encx_lstm_sync_read): stream-ordered,
 // capturable
@@ -298,7 +310,7 @@ __global__ __launch_bounds__(FW * 64) void lstm_fwd_pers(const float* xt, const 
     const bool silent = (ctl & CTL_FAULT) && blockIdx.x == 0;
     float c = 0.f;
     for (int t = 0; t < T; ++t) {
-        LSTM_TRACE(0, t, 0);
+        LSTM_TRACE(0, blockIdx.x, t, 0);
         f32x4v acc[2] = {(f32x4v){0.f, 0.f, 0.f, 0.f}, (f32x4v){0.f, 0.f, 0.f, 0.f}};
         // ---- input part x_l(t): layer 0 reads xt (written before this launch), layer l > 0
         // waits for h_{l-1}(t) of all NUG workgroups of (l-1, bg)
@@ -306,7 +318,7 @@ __global__ __launch_bounds__(FW * 64) void lstm_fwd_pers(const float* xt, const 
             if (wave == 0 && live) live = poll_ge(cnt_in, NUG * (t + 1), err, spins);
             __syncthreads();
         }
-        LSTM_TRACE(0, t, 1);
+        LSTM_TRACE(0, blockIdx.x, t, 1);
         {  // k-groups g < G / 2 of every wave lie in the input half (H % 128 == 0)
             float4 a[G / 2];
             const uint32_t rb = (uint32_t)(((int64_t)arow * T + t) * H + 4 * kk) * 4u;
@@ -322,10 +334,10 @@ __global__ __launch_bounds__(FW * 64) void lstm_fwd_pers(const float* xt, const 
         }
         // ---- recurrent part h_l(t-1) (zero at t = 0): k-groups g >= G / 2
         if (t > 0) {
-            LSTM_TRACE(0, t, 2);
+            LSTM_TRACE(0, blockIdx.x, t, 2);
             if (wave == 0 && live) live = poll_ge(cnt_self, NUG * t, err, spins);
             __syncthreads();
-            LSTM_TRACE(0, t, 3);
+            LSTM_TRACE(0, blockIdx.x, t, 3);
             float4 a[G / 2];
             const uint32_t rb = (uint32_t)(((int64_t)arow * T + t - 1) * H + 4 * kk - H) * 4u;
 #pragma unroll
@@ -344,7 +356,7 @@ __global__ __launch_bounds__(FW * 64) void lstm_fwd_pers(const float* xt, const 
 #pragma unroll
             for (int q = 0; q < 4; ++q) red[wave][kk * 4 + q][16 * cc + col] = acc[cc][q];
         __syncthreads();
-        LSTM_TRACE(0, t, 4);
+        LSTM_TRACE(0, blockIdx.x, t, 4);
         if (pact) {
             float pre[4];
 #pragma unroll
@@ -367,13 +379,13 @@ __global__ __launch_bounds__(FW * 64) void lstm_fwd_pers(const float* xt, const 
             for (int q = 0; q < 4; ++q) gs[q * H + pu] = g4[q];
         }
         // publish: every storing wave drained, a barrier, one lane's arrival
-        LSTM_TRACE(0, t, 5);
+        LSTM_TRACE(0, blockIdx.x, t, 5);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        LSTM_TRACE(0, t, 6);
+        LSTM_TRACE(0, blockIdx.x, t, 6);
         if (tid == 0 && !silent) __hip_atomic_fetch_add(cnt_self, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    finish_launch(sync, (int)gridDim.x / NUG, NUG * T, 0, 0);  // the L NBG counters
+    finish_launch(sync, {(int)gridDim.x / NUG, NUG * T});  // the L NBG counters
 }
 
 // ------------------------------------------------------------------------- backward step
@@ -540,65 +552,125 @@ __global__ __launch_bounds__(BW * 64) void lstm_bwd_gemm(const float* DA, const 
 }
 
 // ------------------------------------------------------------------------- persistent backward
-// ONE launch runs the backward recurrence of all layers (option LSTM_PERSIST). Workgroup
-// (l, bg, ct) owns the 16 columns n = 16 ct .. of P_l = DA_l . wcat_l (K = 4H) for the 16 batch
-// rows of bg, with its slice of wcatT_l ([16][4H], 128 KB at H = 512) resident in registers:
+// ONE launch runs the backward recurrence of all layers (option LSTM_PERSIST). The unit of work is
+// one K-split of a column tile: workgroup (l, bg, nt, s) owns the 64 columns n = 64 nt .. of
+// P_l = DA_l . wcat_l (K = 4H) over the k-groups [s H/16, (s + 1) H/16) of split s, for the 16
+// batch rows of bg, with its slice of wcatT_l ([64][H], 128 KB at H = 512) resident in registers.
+// Per contracted frame:
+//   stage     the 512 threads copy DA_l(tf)[16 rows][H floats of split s] into LDS once (sc1 b128
+//             loads); the four 16-column sub-tile wave pairs read their A fragments from that copy
+//             (each DA row reaches the CU once per frame, a quarter of it);
+//   MFMA      wave w runs chains 2 (w & 1) + h, h = 0, 1, of split s for sub-tile w >> 1, k-group g
+//             ascending, q inner; the four chains of a sub-tile are summed through `red` in chain
+//             order: the split's partial tile [16][64], the bits of lstm_bwd_gemm's P[s];
+//   exchange  the partial is stored (sc1) into this workgroup's ring slot and published on the
+//             counter of (l, bg, nt); after the tile's four arrivals the workgroup loads the four
+//             partials of ITS quarter of the tile (columns 64 nt + 16 s ..) and adds them in
+//             ascending split order, as lstm_bwd_elem does.
+// From there workgroup (nt, s) is the column tile ct = 4 nt + s of 16 x 16 points:
 //   ct >= H/16 (recurrent tile, units u = 16 (ct - H/16) ..): frame t takes the recurrent grad of
 //     h_l(t) from DA_l(t+1), adds the grad from above (dout for the top layer, else the input-grad
-//     tile of layer l+1 for the same units and frame, handed over by workgroup (l+1, bg, ct - H/16)),
-//     runs the cell backward of its 16 x 16 points (dc kept in registers across frames) and
+//     tile of layer l+1 for the same units and frame, handed over by the workgroup of (l+1, bg) with
+//     ct - H/16), runs the cell backward of its points (dc kept in registers across frames) and
 //     publishes DA_l(t) of its units;
 //   ct < H/16 (input tile): frame t contracts DA_l(t) into the input grad of layer l (dx for l = 0,
 //     else handed to the recurrent tile of layer l-1).
-// The hand-offs are those of lstm_fwd_pers (write-through stores, drain, barrier, one arrival;
-// sc1 loads after a bounded poll). The contraction keeps the exact split structure of
-// lstm_bwd_gemm + lstm_bwd_elem (4 splits of the 4H/16 k-groups, each 4 interleaved chains summed
-// in chain order, the splits summed in ascending order), so both forms give the same bits: wave w
-// runs chains (s, c) = (w / 2, 2 (w % 2) + h), h = 0, 1, of G k-groups each (H % 128 == 0, G = H/64).
-// grid L * NBG * 2H/16, FW waves. XP [L-1][B][T][H]: the input-grad tiles between layers.
+// A 64-column tile lies wholly in one half (H % 64 == 0), so its four workgroups contract the same
+// frames: the recurrent tiles' first frame has nothing to contract and skips the exchange in all
+// four alike. The hand-offs are those of lstm_fwd_pers (write-through stores, drain, barrier, one
+// arrival; sc1 loads after a bounded poll). G = H / 64 k-groups per chain (H % 128 == 0).
+// grid L * NBG * 2H/64 * 4 (= L NBG H/8), FW waves. XP [L-1][B][T][H]: the input-grad tiles between
+// layers. EX [2][grid][16][64]: the exchange ring.
+//
+// The ring is two deep, indexed by frame parity. A workgroup's slot i % 2 is rewritten at frame
+// i + 2, after the workgroup has passed the exchange poll of frame i + 1, i.e. after every sibling
+// has published frame i + 1; a sibling publishes behind its s_waitcnt vmcnt(0) + barrier, which
+// are later in its program than its loads of frame i. So every reader of slot i % 2 is done
+// before the rewrite. This holds for every tile alike, layer 0's input tiles (which wait on DA
+// only) included: the argument uses the exchange polls alone. (After a timed-out poll the order
+// is lost with the results; the error word says so.)
+//
+// Workgroup ids: blocks are dealt round-robin over the 8 XCDs, so block b's logical index is
+// (b % 8) (grid / 8) + b / 8 with nt fastest: the grid/8 workgroups of one XCD cover as few
+// (l, bg, s) slices of DA as possible (2 at the config-3 size) and an XCD's L2 refetches a quarter
+// of a group's DA rows per frame. For speed only; nothing depends on the placement.
+//
+// Measured (tools/lstm_trace.py, profiles/lstm_bwd, B 32, H 512, T 75, L 2): a frame takes 7.1 us
+// (poll DA 1.5-2.2 of which the hand-off is 1.3-1.7, stage 0.7-1.0, MFMA + chain sum 2.2 against the
+// 1.7 of the CU's FP32 MFMA rate, exchange 1.3-1.5, point phase 0.2-0.5, drain 0.3), 561 us per call;
+// with the whole K in one workgroup (every workgroup loading all 16 x 4H of DA, 128 KB, from L2) the
+// frame took 9.8 us, 5.1 of it load + MFMA, 798 us per call.
+constexpr int RED_S = 68;  // row stride of red (floats): ds_write_b32 of rows 4 kk + q conflict-free
 template <int G>
 __global__ __launch_bounds__(FW * 64) void lstm_bwd_pers(const float* dout, const float* wcatT, const float* Cst,
                                                          const float* Gs, float* DA, float* dx, int acc_x,
-                                                         float* XP, int B, int T, int H, int L, int NBG,
+                                                         float* XP, float* EX, int B, int T, int H, int L, int NBG,
                                                          int* sync, int ctl) {
-    const int NRT = H / 16, NCT = 2 * NRT;
-    const int id = blockIdx.x, ct = id % NCT, bg = (id / NCT) % NBG, l = id / (NCT * NBG);
-    const bool recw = ct >= NRT;
+    // row stride of the staged DA slice (floats): + 8 puts the 16-lane groups of ds_read_b128 on 16
+    // distinct 16-byte slots (slot 2 col + kk)
+    constexpr int AS = 64 * G + 8;
+    constexpr int NS = G / 2;  // staging float4s per thread: 16 rows x 16 G / 512
+    const int NRT = H / 16, NT = H / 32, NTH = NT / 2;
+    const int nwg = (int)gridDim.x;  // (a multiple of 16)
+    const int id = (int)(blockIdx.x & 7) * (nwg >> 3) + (int)(blockIdx.x >> 3);
+    const int nt = id % NT, s = (id / NT) & 3, bg = (id / (4 * NT)) % NBG, l = id / (4 * NT * NBG);
+    const int ct = 4 * nt + s;
+    const bool recw = nt >= NTH;
     const int ut = recw ? ct - NRT : ct;
-    __shared__ float red[16][16][17];
+    __shared__ __attribute__((aligned(16))) float sa[16 * AS];
+    __shared__ __attribute__((aligned(16))) float red[4][16][RED_S];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 15, kk = lane >> 4;
-    const int K = 4 * H, gper = 4 * G;
+    const int K = 4 * H;
     const int64_t BTH = (int64_t)B * T * H;
     float4 wr[2][G];
     {
-        const float* Wt = wcatT + (int64_t)l * 2 * H * K + (int64_t)(ct * 16 + col) * K;
+        const float* Wt = wcatT + (int64_t)l * 2 * H * K + (int64_t)(64 * nt + 16 * (wave >> 1) + col) * K + s * H;
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
-            for (int g = 0; g < G; ++g)
-                wr[h][g] = ld4(Wt + ((wave >> 1) * gper + 2 * (wave & 1) + h + 4 * g) * 16 + 4 * kk);
+            for (int g = 0; g < G; ++g) wr[h][g] = ld4(Wt + (2 * (wave & 1) + h + 4 * g) * 16 + 4 * kk);
     }
     const __amdgpu_buffer_rsrc_t rda = buf_rsrc(DA + l * 4 * BTH, (uint32_t)(BTH * 16));
     const __amdgpu_buffer_rsrc_t rxp = buf_rsrc(XP, (uint32_t)((L > 1 ? L - 1 : 1) * BTH * 4));
-    const int arow = min(bg * 16 + col, B - 1);
+    const __amdgpu_buffer_rsrc_t rex = buf_rsrc(EX, (uint32_t)nwg * 8192u);
+    // staging: float4 f = tid + 512 j of the slice [16][16 G float4]
+    uint32_t sg[NS];  // float offset in DA_l of the float4's row at frame 0, + the split's columns
+    int sl[NS];       // float offset in sa
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int f = tid + FW * 64 * j, r = f / (16 * G), c4 = f % (16 * G);
+        sg[j] = (uint32_t)((int64_t)min(bg * 16 + r, B - 1) * T * K + s * H + 4 * c4);
+        sl[j] = r * AS + 4 * c4;
+    }
     // point phase: thread p < 256 owns (row 16 bg + p / 16, unit 16 ut + p % 16)
     const int pr = tid >> 4, pu = ut * 16 + (tid & 15), pb = bg * 16 + pr;
     const bool pact = tid < 256 && pb < B;
     const int pbc = min(pb, B - 1);
     const float* Cl = Cst + l * BTH;
     const float* Gl = Gs + l * 4 * BTH;
+    // the exchange: this workgroup's partial tile at float (slot nwg + tile 4 + s) 1024 of EX, stored
+    // as float4 (row pr, columns 4 xc ..: rotated by the row so that the ds_read_b128 of red is
+    // conflict-free); loaded as the 16 columns 16 s .. of the four partials of the tile
+    const int xr = pr & 15, xc = ((tid & 15) - xr) & 15;
+    const uint32_t xbase = (uint32_t)(((l * NBG + bg) * NT + nt) * 4) * 4096u;
+    const uint32_t xst = xbase + (uint32_t)(s * 1024 + xr * 64 + 4 * xc) * 4u;
+    const uint32_t xld = xbase + (uint32_t)(xr * 64 + 16 * s + (tid & 15)) * 4u;
     int* const cnt_da = sync + (l * NBG + bg) * SYNC_LINE;  // DA_l rows of bg: NRT arrivals per frame
     int* const xf_out = sync + (L * NBG + ((l > 0 ? l - 1 : 0) * NBG + bg) * NRT + ut) * SYNC_LINE;
     const int* const xf_in = sync + (L * NBG + (l * NBG + bg) * NRT + ut) * SYNC_LINE;
+    // the tile's exchange counter: 4 arrivals per contracted frame (input tiles' lines first)
+    int* const cnt_ex = sync + (L * NBG + (L - 1) * NBG * NRT + (recw ? L * NBG * NTH : 0) + (l * NBG + bg) * NTH +
+                                (recw ? nt - NTH : nt)) * SYNC_LINE;
     int* const err = sync + SYNC_LINES * SYNC_LINE;
     const bool top = l == L - 1;
     bool live = true;
     const int spins = ctl_spins(ctl);
-    const bool silent = (ctl & CTL_FAULT) && blockIdx.x == NRT;  // layer 0's first recurrent tile
+    // layer 0's first recurrent workgroup (first row group, split 0)
+    const bool silent = (ctl & CTL_FAULT) && l == 0 && bg == 0 && nt == NTH && s == 0;
     float dcn = 0.f;
     for (int i = 0; i < T; ++i) {
         const int t = T - 1 - i;
-        LSTM_TRACE(1, i, 0);
+        LSTM_TRACE(1, id, i, 0);
         // the point phase's own operands (forward state, dout): loaded after the poll (a poll's
         // wait would otherwise wait for them), ahead of the DA loads
         float ig = 0.f, fg = 0.f, gg = 0.f, og = 0.f, c = 0.f, cpl = 0.f, dtop = 0.f;
@@ -621,18 +693,23 @@ __global__ __launch_bounds__(FW * 64) void lstm_bwd_pers(const float* dout, cons
         if (tf < T) {
             if (wave == 0 && live) live = poll_ge(cnt_da, NRT * (T - tf), err, spins);
             __syncthreads();
-            LSTM_TRACE(1, i, 1);
-            load_point();  // (older than the DA loads: the MFMAs' in-order waits are not pushed back)
+            LSTM_TRACE(1, id, i, 1);
+            load_point();  // (older than the DA loads: the waits on those do not wait for younger loads)
+            {
+                float4 v[NS];
+#pragma unroll
+                for (int j = 0; j < NS; ++j) v[j] = ld4_sc1(rda, (sg[j] + (uint32_t)(tf * K)) * 4u);
+#pragma unroll
+                for (int j = 0; j < NS; ++j) *reinterpret_cast<float4*>(sa + sl[j]) = v[j];
+            }
+            __syncthreads();
+            LSTM_TRACE(1, id, i, 2);
             float4 a[2][G];
-            const uint32_t rb = (uint32_t)(((int64_t)arow * T + tf) * K + 4 * kk) * 4u;
-            // issued in the order the MFMAs consume them (k-group g of both chains), so the chains
-            // start as the first loads land instead of after half of them
+            const float* ap = sa + col * AS + (2 * (wave & 1)) * 16 + 4 * kk;
 #pragma unroll
             for (int g = 0; g < G; ++g)
 #pragma unroll
-                for (int h = 0; h < 2; ++h)
-                    a[h][g] = ld4_sc1(rda, rb + (uint32_t)((wave >> 1) * gper + 2 * (wave & 1) + h + 4 * g) * 64u);
-            __builtin_amdgcn_sched_barrier(0);
+                for (int h = 0; h < 2; ++h) a[h][g] = *reinterpret_cast<const float4*>(ap + (h + 4 * g) * 16);
             f32x4v acc[2] = {(f32x4v){0.f, 0.f, 0.f, 0.f}, (f32x4v){0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
             for (int g = 0; g < G; ++g)
@@ -643,21 +720,40 @@ __global__ __launch_bounds__(FW * 64) void lstm_bwd_pers(const float* dout, cons
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) red[2 * wave + h][kk * 4 + q][col] = acc[h][q];
+                for (int q = 0; q < 4; ++q) red[2 * (wave & 1) + h][kk * 4 + q][16 * (wave >> 1) + col] = acc[h][q];
             __syncthreads();
-            LSTM_TRACE(1, i, 2);
+            // the split's partial tile: the chains in chain order, four columns per thread
             if (tid < 256) {
-                const int r = tid >> 4, cc = tid & 15;
+                f32x4v p = *reinterpret_cast<const f32x4v*>(&red[0][xr][4 * xc]);
+#pragma unroll
+                for (int w = 1; w < 4; ++w) p += *reinterpret_cast<const f32x4v*>(&red[w][xr][4 * xc]);
+                LSTM_TRACE(1, id, i, 3);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, p), rex,
+                                                       (int)(xst + (uint32_t)(i & 1) * (uint32_t)nwg * 4096u), 0, SC1);
+            }
+            // publish the partial (drain, barrier, one arrival), wait for the tile's four
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (tid == 0 && !silent) __hip_atomic_fetch_add(cnt_ex, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (wave == 0 && live) live = poll_ge(cnt_ex, 4 * (recw ? i : i + 1), err, spins);
+            __syncthreads();
+            if (tid < 256) {
+                float v[4];
+#pragma unroll
+                for (int w = 0; w < 4; ++w)
+                    v[w] = __builtin_bit_cast(
+                        float, __builtin_amdgcn_raw_buffer_load_b32(
+                                   rex, (int)(xld + (uint32_t)(i & 1) * (uint32_t)nwg * 4096u + (uint32_t)w * 4096u), 0,
+                                   SC1));
                 float tot = 0.f;
 #pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    float v = red[4 * s][r][cc];
-#pragma unroll
-                    for (int w = 1; w < 4; ++w) v += red[4 * s + w][r][cc];
-                    tot += v;
-                }
+                for (int w = 0; w < 4; ++w) tot += v[w];
                 tile = tot;
             }
+#ifdef ENCX_LSTM_TRACE
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stamp after the partials have landed
+#endif
+            LSTM_TRACE(1, id, i, 4);
         } else {
             load_point();
         }
@@ -683,7 +779,7 @@ __global__ __launch_bounds__(FW * 64) void lstm_bwd_pers(const float* dout, cons
             if (!top) {
                 if (wave == 0 && live) live = poll_ge(xf_in, i + 1, err, spins);
                 __syncthreads();
-                LSTM_TRACE(1, i, 3);
+                LSTM_TRACE(1, id, i, 5);
                 if (tid < 256)
                     above = __builtin_bit_cast(
                         float, __builtin_amdgcn_raw_buffer_load_b32(rxp, (int)((uint32_t)(l * BTH + o) * 4u), 0, SC1));
@@ -701,16 +797,19 @@ __global__ __launch_bounds__(FW * 64) void lstm_bwd_pers(const float* dout, cons
             }
             publish = true;
         }
-        // publish: every storing wave drained, a barrier (also ends this frame's reads of red), one
+        // publish: every storing wave drained, a barrier (also ends this frame's reads of LDS), one
         // lane's arrival
-        LSTM_TRACE(1, i, 4);
+        LSTM_TRACE(1, id, i, 6);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        LSTM_TRACE(1, i, 5);
+        LSTM_TRACE(1, id, i, 7);
         if (publish && tid == 0 && !silent) __hip_atomic_fetch_add(pub, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    // the DA counters (NRT arrivals per frame) and the input-tile flags (one per frame)
-    finish_launch(sync, L * NBG, NRT * T, (L - 1) * NBG * NRT, T);
+    // the DA counters (NRT arrivals per frame), the input-tile flags (one per frame) and the exchange
+    // counters (4 per contracted frame: every frame of an input tile, all but the first of a
+    // recurrent one)
+    finish_launch(sync, {L * NBG, NRT * T}, {(L - 1) * NBG * NRT, T}, {L * NBG * NTH, 4 * T},
+                  {L * NBG * NTH, 4 * (T - 1)});
 }
 
 // ------------------------------------------------------------------------- layout kernels
@@ -984,16 +1083,38 @@ template <int G> static int fwd_pers_grid(int64_t B, int64_t T, int64_t H, int64
     if (!coresident((const void*)lstm_fwd_pers<G>, nwg)) return 0;
     return (int)nwg;
 }
-// workgroups of the persistent backward, or 0 (as fwd_pers_grid; plus the hand-off lines)
-// (DA's buffer offsets cover B T 4H floats, XP's (L - 1) B T H: both must fit the 32-bit offsets)
-template <int G> static int bwd_pers_grid(int64_t B, int64_t T, int64_t H, int64_t L) {
-    if (encx_opt(OPT_LSTM_PERSIST) == 0 || H % 128 || H > 512 || B * T * H * 16 >= ((int64_t)1 << 31) ||
-        (L - 1) * B * T * H * 4 >= ((int64_t)1 << 31))
+// what the persistent backward asks of the shape alone (no device call): the widths, the 32-bit
+// buffer offsets (DA's cover B T 4H floats, XP's (L - 1) B T H) and the hand-off lines (the DA
+// counters, the input-tile flags, the exchange counters). -> its workgroups (4 K-splits of every
+// 64-column tile of every layer and row group), or 0
+static int64_t bwd_pers_shape(int64_t B, int64_t T, int64_t H, int64_t L) {
+    if (H % 128 || H > 512 || B * T * H * 16 >= ((int64_t)1 << 31) || (L - 1) * B * T * H * 4 >= ((int64_t)1 << 31))
         return 0;
-    const int64_t nbg = cdiv(B, 16), nwg = L * nbg * (2 * H / 16);
-    if (L * nbg + (L - 1) * nbg * (H / 16) > SYNC_LINES || nwg > device_cus() || !sync_words()) return 0;
+    const int64_t nbg = cdiv(B, 16);
+    if (L * nbg + (L - 1) * nbg * (H / 16) + L * nbg * (2 * H / 64) > SYNC_LINES) return 0;
+    return L * nbg * (2 * H / 64) * 4;
+}
+// floats of the split-exchange ring of the persistent backward: two slots of a [16][64] partial tile
+// per workgroup (0 where the shape does not admit the form)
+static size_t bwd_pers_ring(int64_t B, int64_t T, int64_t H, int64_t L) {
+    return (size_t)bwd_pers_shape(B, T, H, L) * 2 * 16 * 64;
+}
+// workgroups of the persistent backward, or 0 (as fwd_pers_grid; plus the hand-off lines)
+template <int G> static int bwd_pers_grid(int64_t B, int64_t T, int64_t H, int64_t L) {
+    const int64_t nwg = bwd_pers_shape(B, T, H, L);
+    if (encx_opt(OPT_LSTM_PERSIST) == 0 || !nwg || nwg > device_cus() || !sync_words()) return 0;
     if (!coresident((const void*)lstm_bwd_pers<G>, nwg)) return 0;
     return (int)nwg;
+}
+// bwd_pers_grid of the shape's instantiation (G = H / 64)
+static int bwd_pers_grid_any(int64_t B, int64_t T, int64_t H, int64_t L) {
+    switch (H % 64 ? 0 : H / 64) {
+        case 2: return bwd_pers_grid<2>(B, T, H, L);
+        case 4: return bwd_pers_grid<4>(B, T, H, L);
+        case 6: return bwd_pers_grid<6>(B, T, H, L);
+        case 8: return bwd_pers_grid<8>(B, T, H, L);
+        default: return 0;
+    }
 }
 template <int G>
 static bool fwd_pers_launch(hipStream_t st, const float* xt, const float* wcat, const float* bsum, float* Y,
@@ -1009,8 +1130,9 @@ static bool bwd_pers_launch(hipStream_t st, const float* dout, const float* wcat
                             float* DA, float* dx, int acc_x, float* XP, int B, int T, int H, int L) {
     const int nwg = bwd_pers_grid<G>(B, T, H, L);
     if (!nwg) return false;
+    float* EX = XP + (int64_t)(L > 1 ? L - 1 : 1) * B * T * H;  // the exchange ring follows XP
     hipLaunchKernelGGL((lstm_bwd_pers<G>), dim3((unsigned)nwg), dim3(FW * 64), 0, st, dout, wcatT, Cst, Gs, DA, dx,
-                       acc_x, XP, B, T, H, L, (int)cdiv(B, 16), sync_words(), pers_ctl());
+                       acc_x, XP, EX, B, T, H, L, (int)cdiv(B, 16), sync_words(), pers_ctl());
     return true;
 }
 
@@ -1111,10 +1233,15 @@ int encx_lstm_sync_read(int32_t* count, encx_stream_t stream) {
 
 size_t encx_lstm_bwd_workspace(int64_t B, int64_t T, int64_t H, int64_t L) {
     // step form: dcn [L][B][H], P [L][ns][B][2H], the fused step's arrival counters [(L + 1) * H/16]
-    // (int); persistent form: XP [L-1][B][T][H]
+    // (int); persistent form: XP [L-1][B][T][H], then the split-exchange ring [2][workgroups][16][64]
+    // (counted wherever the shape admits the form, whatever the options and the device say)
     const size_t step = (size_t)L * B * H + (size_t)L * bwd_splits(H) * B * 2 * H + (size_t)(L + 1) * (H / 16);
-    const size_t pers = (size_t)(L > 1 ? L - 1 : 1) * B * T * H;
+    const size_t pers = (size_t)(L > 1 ? L - 1 : 1) * B * T * H + bwd_pers_ring(B, T, H, L);
     return (step > pers ? step : pers) * sizeof(float);
+}
+
+int encx_lstm_bwd_form(int64_t B, int64_t T, int64_t H, int64_t L) {
+    return lstm_shape_ok(B, T, H, L) && bwd_pers_grid_any(B, T, H, L) > 0 ? 1 : 0;
 }
 
 int encx_lstm_bwd(const float* dout, const float* wcatT, const float* Cst, const float* Gs, float* DA, float* dx,

@@ -378,7 +378,18 @@ int encx_lstm_pack(const float* w_ih, const float* w_hh, const float* b_ih, cons
 int encx_lstm_fwd(const float* x, const float* wcat, const float* bsum, float* xt, float* Y, float* Cst,
                   float* Gs, float* out, int skip, int64_t B, int64_t T, int64_t H, int64_t L,
                   encx_stream_t stream);
+/* Bytes of encx_lstm_bwd's workspace: the larger of what its two forms need. Step form: the
+ * carried cell grads, the K-split partials and the fused step's counters. Persistent form: the
+ * input-grad tiles handed between layers ([L-1][B][T][H]) followed by the ring through which the
+ * workgroups of a column tile exchange their K-split partials (two [16][64] slots per workgroup,
+ * about 2 MB at B 32, H 512, L 2); the ring is counted for every shape that admits the persistent
+ * form (H % 128 == 0, H <= 512, the hand-off lines), whatever the options and the device. The
+ * library allocates nothing. */
 size_t encx_lstm_bwd_workspace(int64_t B, int64_t T, int64_t H, int64_t L);
+/* Host-only query: 1 if encx_lstm_bwd would run this shape in the persistent form under the current
+ * options on the current device (the shape, option LSTM_PERSIST, every workgroup resident at
+ * once), 0 if it would take the step form. Not an error code. */
+int encx_lstm_bwd_form(int64_t B, int64_t T, int64_t H, int64_t L);
 /* Backward through time of all layers from dout [B][H][T] (the grad of the LSTM output, before
  * the skip): the gate pre-activation grads DA [L][B][T][4H] and the input grad dx [B][H][T]
  * (added when acc_x; NULL to skip). ws: encx_lstm_bwd_workspace bytes. */

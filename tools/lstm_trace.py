@@ -59,28 +59,31 @@ def main():
         got = sel[:, 1:, 3]
         print(f'    h hand-off: last producer publish -> consumer poll done: median '
               f'{np.median(got - pub[None, :-1]):.2f} us, max {np.max(got - pub[None, :-1]):.2f}')
-    # ---- backward: workgroup (l, bg, ct), NCT = 2H / 16
-    nct = 2 * H // 16
-    nwg = L * nbg * nct
+    # ---- backward: logical workgroup index ((l nbg + bg) 4 + s) NT + nt, NT = 2H / 64 column tiles of
+    # 4 K-splits each; tiles nt >= NT / 2 are recurrent. Points: 0 frame start, 1 DA poll done, 2 DA
+    # staged in LDS, 3 MFMA + chain sum done, 4 the four partials of the tile landed, 5 poll x done
+    # (recurrent tiles below the top layer), 6 point phase issued, 7 drained
+    ntile = 2 * H // 64
+    nwg = L * nbg * 4 * ntile
     bw = tr[1, :nwg, :T]
     print(f'backward: {nwg} workgroups, frame cadence {np.median(np.diff(bw[:, :, 0], axis=1)):.2f} us; whole '
-          f'recurrence {bw[:, T - 1, 5].max() - bw[:, 0, 0].min():.1f} us')
-    nrt = H // 16
+          f'recurrence {bw[:, T - 1, 7].max() - bw[:, 0, 0].min():.1f} us')
     for l in range(L):
-        for kind, cts in (('recurrent', range(nrt, nct)), ('input', range(nrt))):
-            ids = [(l * nbg + b) * nct + c for b in range(nbg) for c in cts]
+        for kind, nts in (('recurrent', range(ntile // 2, ntile)), ('input', range(ntile // 2))):
+            ids = [((l * nbg + b) * 4 + sp) * ntile + n for b in range(nbg) for sp in range(4) for n in nts]
             s = bw[ids][:, 1:]
             seg = lambda a, b: np.median(s[:, :, b] - s[:, :, a])
-            print(f'  layer {l} {kind}: poll DA {seg(0, 1):.2f}, load+MFMA+LDS {seg(1, 2):.2f}, '
-                  f'{"poll x " + format(seg(2, 3), ".2f") + ", " if kind == "recurrent" and l < L - 1 else ""}'
-                  f'point phase {seg(3 if kind == "recurrent" and l < L - 1 else 2, 4):.2f}, drain+barrier {seg(4, 5):.2f}, '
-                  f'to next frame {np.median(s[:, 1:, 0] - s[:, :-1, 5]):.2f}')
-        rid = [(l * nbg + b) * nct + c for b in range(nbg) for c in range(nrt, nct)]
-        pub = bw[rid][:, :, 5].max(axis=0)
+            pollx = kind == 'recurrent' and l < L - 1
+            print(f'  layer {l} {kind}: poll DA {seg(0, 1):.2f}, stage {seg(1, 2):.2f}, MFMA+reduce {seg(2, 3):.2f}, '
+                  f'exchange {seg(3, 4):.2f}, {"poll x " + format(seg(4, 5), ".2f") + ", " if pollx else ""}'
+                  f'point {seg(5 if pollx else 4, 6):.2f}, drain {seg(6, 7):.2f}, '
+                  f'to next frame {np.median(s[:, 1:, 0] - s[:, :-1, 7]):.2f}')
+        rid = [((l * nbg + b) * 4 + sp) * ntile + n for b in range(nbg) for sp in range(4)
+               for n in range(ntile // 2, ntile)]
+        pub = bw[rid][:, :, 7].max(axis=0)
         got = bw[rid][:, 1:, 1]
         print(f'    DA hand-off (recurrent tiles): last publish -> poll done: median '
               f'{np.median(got - pub[None, :-1]):.2f} us')
-
 
 if __name__ == '__main__':
     main()
