@@ -24,6 +24,13 @@
 //                grid-wide dependency (no inter-workgroup waiting, no counters).
 //  roll_kernel   end of step: every window's last P columns move to its front, ONE launch driven
 //                by a device table; first chunk: the reflected columns x[P] .. x[1] instead.
+//
+// Slots (encx_stream_roll_slots, encx_stream_lstm_slots): the streams of a session join, leave,
+// sit a step out and deliver their own frame counts. A step computes max(frames) columns for
+// every slot: every layer is causal, so the columns past a slot's count influence nothing that is
+// carried, and stream_gemm needs no mask. Only what carries state reads the per-slot counts from a
+// slot table in device memory: roll_kernel and lstm_stage / lstm_cell, the same kernels, which
+// run without a table for the uniform step.
 #include "common.h"
 
 namespace {
@@ -153,23 +160,38 @@ int launch_gemm(const GemmP& p, int act, hipStream_t st) {
 // ------------------------------------------------------------------------- LSTM around the GEMM
 ENCX_DEV float sigm_s(float x) { return 1.f / (1.f + expf(-x)); }
 
-// hz[0][b][u] = x[b][u][t]: layer 0's input of step t
-__global__ void lstm_stage(const float* x, int64_t xbs, int64_t xrs, int t, float* hz, int B, int H) {
+// The slot table (encx.h): slots[2b] = frames slot b delivers this step (0: it sits out),
+// slots[2b + 1] = 1 on the slot's first chunk. NULL: every slot delivers every frame of the call.
+
+// hz[0][b][u] = x[b][u][t]: layer 0's input of step t. A slot's first chunk starts from h = c = 0
+// in every layer: cleared here, before the first gate GEMM reads h, so a restarted slot costs no
+// launch of its own.
+__global__ void lstm_stage(const float* x, int64_t xbs, int64_t xrs, int t, float* hz, float* c, int B, int H,
+                           int L, const int32_t* slots) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * H) return;
     const int b = i / H, u = i - b * H;
     hz[(int64_t)b * 2 * H + u] = x[(int64_t)b * xbs + (int64_t)u * xrs + t];
+    if (slots && t == 0 && slots[2 * b + 1] && slots[2 * b] > 0) {
+        for (int l = 0; l < L; ++l) {
+            hz[((int64_t)l * B + b) * 2 * H + H + u] = 0.f;
+            c[((int64_t)l * B + b) * H + u] = 0.f;
+        }
+    }
 }
 
 // layer l, one (b, u) per thread: gates i, f, g, o from pre [B][4H]; c and h carried in place
 // (h in the second half of the layer's own step input hz[l]); h also becomes the next layer's
-// input, or the output column t (+ x, the skip) after the last layer
+// input, or the output column t (+ x, the skip) after the last layer. A slot that has no frame t
+// keeps c, h and its output column as they are.
 __global__ void lstm_cell(const float* pre, float* hz, float* c, const float* x, int64_t xbs, int64_t xrs,
-                          float* out, int64_t obs, int64_t ors, int t, int skip, int last, int B, int H) {
+                          float* out, int64_t obs, int64_t ors, int t, int skip, int last, int B, int H,
+                          const int32_t* slots) {
 #pragma clang fp contract(on)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * H) return;
     const int b = i / H, u = i - b * H;
+    if (slots && t >= slots[2 * b]) return;
     const float* pr = pre + (int64_t)b * 4 * H + u;
     const float ig = sigm_s(pr[0]), fg = sigm_s(pr[H]), gg = tanhf(pr[2 * H]), og = sigm_s(pr[3 * H]);
     const float cn = fg * c[i] + ig * gg;
@@ -190,24 +212,88 @@ __global__ void lstm_cell(const float* pre, float* hz, float* c, const float* x,
 // when n_cols < P, so every lane loads its column before any lane stores (one load instruction,
 // then one store instruction, for the whole wave: P <= 64). Reflect (a stream's first chunk):
 // column c <- column 2P - c, i.e. the history is x[P], x[P-1], .., x[1] as pad1d writes it.
-__global__ __launch_bounds__(256) void roll_kernel(const encx_stream_win* wins, int n, int64_t rows_total,
-                                                   int reflect) {
+// Zero (a first chunk whose history is the transposed conv's previous column): columns [0, P) <- 0.
+//
+// The table holds entries of esz bytes that begin with an encx_stream_win. Without a slot table
+// (encx_stream_roll) every row moves the entry's n_cols. With one (encx_stream_roll_slots) the
+// entries are encx_stream_slot_win: row r of a window belongs to slot b = r / chans and moves
+// slots[2b] * rate columns; a slot that sits out keeps its history, and reflect / zero touch
+// only the rows of slots on their first chunk. A row whose move would leave the row is skipped:
+// whatever the tables hold, no address outside [0, rstride) of a row is formed.
+__global__ __launch_bounds__(256) void roll_kernel(const char* tab, int esz, int n, int64_t rows_total, int mode,
+                                                   const int32_t* slots, int B) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows_total) return;
     int lo = 0, hi = n - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
-        if (wins[mid].row0 <= row) lo = mid;
+        if (((const encx_stream_win*)(tab + (int64_t)mid * esz))->row0 <= row) lo = mid;
         else hi = mid - 1;
     }
-    const encx_stream_win e = wins[lo];
+    const encx_stream_win e = *(const encx_stream_win*)(tab + (int64_t)lo * esz);
     const int P = (int)e.P;
-    if (lane >= P || row - e.row0 >= e.rows) return;
+    if (lane >= P || row < e.row0 || row - e.row0 >= e.rows) return;
+    int64_t n_cols = e.n_cols;
+    if (slots) {
+        const encx_stream_slot_win* s = (const encx_stream_slot_win*)(tab + (int64_t)lo * esz);
+        const int64_t chans = s->chans, rate = s->rate;
+        // rows_total < 2^32 (the launch): a 32-bit division; rate < 2^31 keeps frames * rate exact
+        if (chans <= 0 || chans >= (1ll << 31) || rate <= 0 || rate >= (1ll << 31)) return;
+        const unsigned b = (unsigned)(row - e.row0) / (unsigned)chans;
+        if (b >= (unsigned)B) return;
+        const int frames = slots[2 * b], first = slots[2 * b + 1];
+        if (frames <= 0 || (mode != ENCX_ROLL_SHIFT && !first)) return;
+        n_cols = frames * rate;
+    }
     float* p = e.ptr + (row - e.row0) * e.rstride;
-    const int64_t src = reflect ? 2 * (int64_t)P - lane : e.n_cols + lane;
+    if (mode == ENCX_ROLL_ZERO) {
+        if (P <= e.rstride) p[lane] = 0.f;
+        return;
+    }
+    if (n_cols < 0 || n_cols + P > e.rstride || (mode == ENCX_ROLL_REFLECT && n_cols <= P)) return;
+    const int64_t src = mode == ENCX_ROLL_REFLECT ? 2 * (int64_t)P - lane : n_cols + lane;
     const float v = p[src];
     p[lane] = v;
+}
+
+// the recurrence behind encx_stream_lstm (slots == NULL) and encx_stream_lstm_slots
+int lstm_run(const float* x, const float* wcatT, const float* bsum, float* hz, float* c, float* gates, float* out,
+             int skip, int64_t B, int64_t n, int64_t H, int64_t L, int64_t x_bstride, int64_t x_rstride,
+             int64_t out_bstride, int64_t out_rstride, const int32_t* slots, hipStream_t st) {
+    ENCX_REQUIRE(x && wcatT && bsum && hz && c && gates && out);
+    ENCX_REQUIRE(B > 0 && B <= 64 && n > 0 && L > 0 && H >= 16 && (H % 16) == 0 && H <= 1024);
+    ENCX_REQUIRE(x_rstride >= n && out_rstride >= n && x_bstride >= H * x_rstride && out_bstride >= H * out_rstride);
+    const unsigned pw = (unsigned)cdiv(B * H, 256);
+    for (int64_t t = 0; t < n; ++t) {
+        hipLaunchKernelGGL(lstm_stage, dim3(pw), dim3(256), 0, st, x, x_bstride, x_rstride, (int)t, hz, c, (int)B,
+                           (int)H, (int)L, slots);
+        ENCX_CHECK_LAUNCH();
+        for (int64_t l = 0; l < L; ++l) {
+            float* hzl = hz + l * B * 2 * H;
+            GemmP p;
+            p.x = hzl; p.w = wcatT + l * 8 * H * H; p.bias = bsum + l * 4 * H; p.y = gates;
+            p.xbs = 2 * H; p.xrs = 1; p.ybs = 4 * H; p.yrs = 1;
+            p.R = (int)(2 * H); p.K = 1; p.M = (int)(4 * H); p.ms = 1; p.s = 1; p.d = 1;
+            p.n_out = 1; p.N = (int)B; p.add = 0;
+            const int rc = launch_gemm(p, ENCX_ACT_NONE, st);
+            if (rc) return rc;
+            hipLaunchKernelGGL(lstm_cell, dim3(pw), dim3(256), 0, st, (const float*)gates, hzl, c + l * B * H, x,
+                               x_bstride, x_rstride, out, out_bstride, out_rstride, (int)t, skip, (int)(l == L - 1),
+                               (int)B, (int)H, slots);
+            ENCX_CHECK_LAUNCH();
+        }
+    }
+    return ENCX_OK;
+}
+
+int roll_run(const void* tab, size_t esz, int64_t n_wins, int64_t rows_total, int mode, const int32_t* slots,
+             int64_t B, hipStream_t st) {
+    ENCX_REQUIRE(tab && n_wins > 0 && n_wins < (1ll << 31) && rows_total > 0 && rows_total < (1ll << 32));
+    hipLaunchKernelGGL(roll_kernel, dim3((unsigned)cdiv(rows_total, 4)), dim3(256), 0, st, (const char*)tab,
+                       (int)esz, (int)n_wins, rows_total, mode, slots, (int)B);
+    ENCX_CHECK_LAUNCH();
+    return ENCX_OK;
 }
 
 }  // namespace
@@ -253,40 +339,30 @@ int encx_stream_convtr1d(const float* win, const float* wp, const float* bias, f
 int encx_stream_lstm(const float* x, const float* wcatT, const float* bsum, float* hz, float* c, float* gates,
                      float* out, int skip, int64_t B, int64_t n, int64_t H, int64_t L, int64_t x_bstride,
                      int64_t x_rstride, int64_t out_bstride, int64_t out_rstride, encx_stream_t stream) {
-    ENCX_REQUIRE(x && wcatT && bsum && hz && c && gates && out);
-    ENCX_REQUIRE(B > 0 && B <= 64 && n > 0 && L > 0 && H >= 16 && (H % 16) == 0 && H <= 1024);
-    ENCX_REQUIRE(x_rstride >= n && out_rstride >= n && x_bstride >= H * x_rstride && out_bstride >= H * out_rstride);
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned pw = (unsigned)cdiv(B * H, 256);
-    for (int64_t t = 0; t < n; ++t) {
-        hipLaunchKernelGGL(lstm_stage, dim3(pw), dim3(256), 0, st, x, x_bstride, x_rstride, (int)t, hz, (int)B,
-                           (int)H);
-        ENCX_CHECK_LAUNCH();
-        for (int64_t l = 0; l < L; ++l) {
-            float* hzl = hz + l * B * 2 * H;
-            GemmP p;
-            p.x = hzl; p.w = wcatT + l * 8 * H * H; p.bias = bsum + l * 4 * H; p.y = gates;
-            p.xbs = 2 * H; p.xrs = 1; p.ybs = 4 * H; p.yrs = 1;
-            p.R = (int)(2 * H); p.K = 1; p.M = (int)(4 * H); p.ms = 1; p.s = 1; p.d = 1;
-            p.n_out = 1; p.N = (int)B; p.add = 0;
-            const int rc = launch_gemm(p, ENCX_ACT_NONE, st);
-            if (rc) return rc;
-            hipLaunchKernelGGL(lstm_cell, dim3(pw), dim3(256), 0, st, (const float*)gates, hzl, c + l * B * H, x,
-                               x_bstride, x_rstride, out, out_bstride, out_rstride, (int)t, skip, (int)(l == L - 1),
-                               (int)B, (int)H);
-            ENCX_CHECK_LAUNCH();
-        }
-    }
-    return ENCX_OK;
+    return lstm_run(x, wcatT, bsum, hz, c, gates, out, skip, B, n, H, L, x_bstride, x_rstride, out_bstride,
+                    out_rstride, nullptr, (hipStream_t)stream);
+}
+
+int encx_stream_lstm_slots(const float* x, const float* wcatT, const float* bsum, float* hz, float* c, float* gates,
+                           float* out, int skip, int64_t B, int64_t n_max, int64_t H, int64_t L, int64_t x_bstride,
+                           int64_t x_rstride, int64_t out_bstride, int64_t out_rstride, const int32_t* slots,
+                           encx_stream_t stream) {
+    ENCX_REQUIRE(slots);
+    return lstm_run(x, wcatT, bsum, hz, c, gates, out, skip, B, n_max, H, L, x_bstride, x_rstride, out_bstride,
+                    out_rstride, slots, (hipStream_t)stream);
 }
 
 int encx_stream_roll(const encx_stream_win* wins, int64_t n_wins, int64_t rows_total, int reflect,
                      encx_stream_t stream) {
-    ENCX_REQUIRE(wins && n_wins > 0 && rows_total > 0 && rows_total < (1ll << 32));
-    hipLaunchKernelGGL(roll_kernel, dim3((unsigned)cdiv(rows_total, 4)), dim3(256), 0, (hipStream_t)stream, wins,
-                       (int)n_wins, rows_total, reflect);
-    ENCX_CHECK_LAUNCH();
-    return ENCX_OK;
+    return roll_run(wins, sizeof(encx_stream_win), n_wins, rows_total, reflect ? ENCX_ROLL_REFLECT : ENCX_ROLL_SHIFT,
+                    nullptr, 0, (hipStream_t)stream);
+}
+
+int encx_stream_roll_slots(const encx_stream_slot_win* wins, int64_t n_wins, int64_t rows_total, int mode,
+                           const int32_t* slots, int64_t B, encx_stream_t stream) {
+    ENCX_REQUIRE(slots && B > 0 && B <= 64);
+    ENCX_REQUIRE(mode == ENCX_ROLL_SHIFT || mode == ENCX_ROLL_REFLECT || mode == ENCX_ROLL_ZERO);
+    return roll_run(wins, sizeof(encx_stream_slot_win), n_wins, rows_total, mode, slots, B, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 
 A causal codec can run live: delivered in chunks, it produces exactly what the offline model
 produces on the whole clip. `StreamEncoder` / `StreamDecoder` keep the state that makes this so
-between calls, for `batch` live streams that advance together, one step per chunk:
+between calls, for `batch` live streams, one step per chunk. Streams that advance together:
 
     enc = StreamEncoder(model, batch=64)            # n_q from model.bandwidth
     dec = StreamDecoder(model, batch=64, n_q=enc.n_q)
@@ -27,11 +27,30 @@ Bit-exact slicing: the kernels' reduction order depends on the layer only, never
 or on the chunk length, so the latents, codes and waveform of a stream are identical however its
 audio was cut into chunks and whichever streams share its batch.
 
+Slots. The `batch` streams of a session are slots with a life of their own: calls begin and end
+at different times, and a late packet sits a step out.
+
+    codes = enc.encode_slots(x, frames)      # x [B, C, max(frames) * hop]; frames: B ints
+    wav = dec.decode_slots(codes, frames)    # codes [B, n_q, max(frames)]
+    enc.restart([5]); dec.restart([5])       # slot 5's caller hung up: its next chunk is a first chunk
+
+Slot b delivers the first frames[b] frames of its row (0: it sits the step out and keeps its
+state); the rest of the row is not read (it may hold anything, NaN included), and the matching
+columns of the results are zero. A slot that has not started, or was restarted, needs a first
+chunk of `min_first_frames`; the other slots are not disturbed, whatever they deliver in the same
+step. A step computes max(frames) columns for every slot and costs what the uniform step of that
+length costs: every layer is causal, so the columns past a slot's count influence nothing that is
+carried, and only the two places that carry state look at the per-slot counts (a slot table in
+device memory, read by the kernels): the window roll / first-chunk fill and the LSTM's h and c
+(csrc/stream.hip). encode(x) / decode(codes) are the uniform case. A slot's results are
+bit-identical to the same stream alone in a session of one. Not supported: a bandwidth (n_q) per
+slot, more than 64 slots, LM-coded streaming, an `.ecdc` container for live streams.
+
 Inference only. Weight-normed weights are prepared once, at construction; call
-refresh_weights() after changing the model. All streams of a session start together (reset());
-restarting one slot is not supported.
+refresh_weights() after changing the model. reset() restarts every slot.
 """
 import dataclasses
+import operator
 import typing as tp
 
 import numpy as np
@@ -46,6 +65,7 @@ from .modules.seanet import SEANetEncoder, SEANetResnetBlock
 
 MAX_BATCH = ops.LSTM_MAX_BATCH
 MAX_HISTORY = 64  # encx_stream_roll moves a window row as one wave
+ROLL_SHIFT, ROLL_REFLECT, ROLL_ZERO = 0, 1, 2  # encx.h ENCX_ROLL_*
 
 
 # ---------------------------------------------------------------------------- the layer plan
@@ -203,6 +223,44 @@ def decoder_plan(model) -> Plan:
     return layer_plan(model.decoder, 1)
 
 
+# ---------------------------------------------------------------------------- per-slot validation
+def _ints(values, what):
+    try:
+        return [operator.index(v) for v in values]
+    except TypeError:
+        raise ValueError(f'encx streaming: {what} must be a sequence of ints') from None
+
+
+def check_frames(started: tp.Sequence[bool], frames, min_first_frames: int, max_frames: int):
+    """frames[b] = latent frames slot b delivers this step, checked against each slot's own state
+    (started[b]: it has had its first chunk). -> (n_max, any_first): the columns the step
+    computes and whether any slot is on its first chunk. Raises ValueError; host data only."""
+    frames = _ints(frames, 'frames')
+    if len(frames) != len(started):
+        raise ValueError(f'encx streaming: frames for {len(frames)} slots, the session has {len(started)}')
+    any_first = False
+    for b, (on, f) in enumerate(zip(started, frames)):
+        if not 0 <= f <= max_frames:
+            raise ValueError(f'encx streaming: a chunk of {f} frames in slot {b} (0..max_frames={max_frames})')
+        if f and not on:
+            if f < min_first_frames:
+                raise ValueError(f'encx streaming: the first chunk of slot {b} needs at least '
+                                 f'{min_first_frames} frames (got {f})')
+            any_first = True
+    if not any(frames):
+        raise ValueError('encx streaming: no slot delivers a frame')
+    return max(frames), any_first
+
+
+def check_restart(slots, batch: int) -> tp.List[int]:
+    """The slot indices of a restart(), each in 0..batch-1 (ValueError otherwise)."""
+    slots = _ints(slots, 'slots')
+    for b in slots:
+        if not 0 <= b < batch:
+            raise ValueError(f'encx streaming: slot {b} (0..{batch - 1})')
+    return slots
+
+
 # ---------------------------------------------------------------------------- a running session
 class _Session:
     """The device side of one SEANet stack: windows, prepared weights, LSTM state, roll tables
@@ -252,7 +310,17 @@ class _Session:
         self._bias: tp.Dict[int, torch.Tensor] = {}
         self._tables: tp.Dict[int, tuple] = {}
         self._graphs: tp.Dict[tuple, tuple] = {}
-        self.started = False
+        self.started = [False] * self.B  # per slot: it has had its first chunk
+        self._fresh = True               # the arena is as reset() left it
+        # the slot table the kernels read (encx.h), refilled before each step of a slots call
+        self._slots = torch.zeros(self.B, 2, device=dev, dtype=torch.int32)
+        self._slots_host: tp.Optional[tuple] = None
+        self._staging = [(torch.zeros(self.B, 2, dtype=torch.int32).pin_memory(), torch.cuda.Event())
+                         for _ in range(4)]
+        self._staged = 0
+        self._slot_graphs: tp.Dict[tuple, tuple] = {}
+        self._cols = torch.arange(max(self._W), device=dev, dtype=torch.int32)
+        self._slot_tab = self._slot_table()
         self.refresh_weights()
 
     # ---- weights
@@ -289,16 +357,45 @@ class _Session:
     # ---- state
     @torch.no_grad()
     def reset(self):
-        """Start a new session: every stream's history and LSTM state cleared."""
+        """Start a new session: every slot restarted, every history and LSTM state cleared."""
         self._arena.zero_()
-        self.started = False
+        self.started = [False] * self.B
+        self._fresh = True
 
-    def _check_chunk(self, n):
-        if n < 1 or n > self.max_frames:
-            raise ValueError(f'encx streaming: a chunk of {n} frames (1..max_frames={self.max_frames})')
-        if not self.started and n < self.min_first_frames:
-            raise ValueError(f'encx streaming: the first chunk of a session needs at least '
-                             f'{self.min_first_frames} frames (got {n})')
+    def restart(self, slots):
+        """The named slots' next non-empty chunk is a first chunk. Host bookkeeping only: the
+        `first` flag of the slot table makes the kernels refill the slot's histories and start its
+        LSTM from zero on that chunk."""
+        for b in check_restart(slots, self.B):
+            self.started[b] = False
+
+    def check_frames(self, frames):
+        return check_frames(self.started, frames, self.min_first_frames, self.max_frames)
+
+    def uniform(self):
+        """Whether a step of n frames for every slot can run without the slot table: all slots
+        are past their first chunk, or none has started and the arena is clear (a restarted slot
+        holds the state of its previous stream, which only the table's `first` flag clears)."""
+        return all(self.started) or self._fresh
+
+    def put_slots(self, frames):
+        """Fill the device slot table for this step. The host runs ahead of the device, so the
+        pinned staging buffers rotate, each guarded by the event of the copy that last read it."""
+        tab = tuple((int(f), int(f > 0 and not on)) for f, on in zip(frames, self.started))
+        if tab == self._slots_host:
+            return
+        buf, ev = self._staging[self._staged]
+        self._staged = (self._staged + 1) % len(self._staging)
+        ev.synchronize()
+        buf.copy_(torch.tensor(tab, dtype=torch.int32))
+        self._slots.copy_(buf, non_blocking=True)
+        ev.record()
+        self._slots_host = tab
+
+    def keep(self, cols, rate):
+        """[B, 1, cols] bool, from the slot table on the device (capturable): the columns of a
+        tensor with `rate` columns per frame that belong to each slot's chunk."""
+        return (self._cols[:cols] < self._slots[:, :1] * rate).unsqueeze(1)
 
     # ---- roll tables
     def _table(self, n):
@@ -320,19 +417,45 @@ class _Session:
             t = self._tables[n] = (tab, len(full), rows, index)
         return t
 
-    def _reflect(self, n, wi, st):
+    def _slot_table(self):
+        """The same for a slots step, as encx_stream_slot_win: the columns a row moves come from
+        the slot table, so one table serves every step."""
+        rows, full, single, index = 0, [], [], {}
+        for wi, (w, W, buf) in enumerate(zip(self.plan.windows, self._W, self.bufs)):
+            if not w.P:
+                continue
+            index[wi] = len(full)
+            e = [buf.data_ptr(), self.B * w.C, w.P, 0, W]
+            full.append(e + [rows, w.C, w.rate])
+            single.append(e + [0, w.C, w.rate])
+            rows += self.B * w.C
+        if not full:
+            return None, 0, 0, index
+        return torch.tensor(np.array(full + single, dtype=np.int64)).to(self.dev), len(full), rows, index
+
+    def _reflect(self, n, wi, st, slots=False):
+        """The first-chunk fill of window wi, right after its producer ran. Without the slot table
+        every row is reflected (a 'zero' window is zero already: the arena is clear); with it,
+        the rows of the slots on their first chunk are reflected or cleared."""
         w = self.plan.windows[wi]
-        if not w.P or w.fill != 'reflect':
+        if not w.P:
             return
-        tab, nfull, _, index = self._table(n)
-        call('encx_stream_roll', tab.data_ptr() + 48 * (nfull + index[wi]), 1, self.B * w.C, 1, st)
+        if slots:
+            tab, nfull, _, index = self._slot_tab
+            call('encx_stream_roll_slots', tab.data_ptr() + 64 * (nfull + index[wi]), 1, self.B * w.C,
+                 ROLL_REFLECT if w.fill == 'reflect' else ROLL_ZERO, self._slots.data_ptr(), self.B, st)
+        elif w.fill == 'reflect':
+            tab, nfull, _, index = self._table(n)
+            call('encx_stream_roll', tab.data_ptr() + 48 * (nfull + index[wi]), 1, self.B * w.C, 1, st)
 
     # ---- one step
-    def _layers(self, n, first):
+    def _layers(self, n, first, slots=False):
+        """The layers and the end-of-step roll for n columns per slot; first: the first-chunk
+        fills run too. slots: masked by the device slot table (n = n_max, first = any slot's)."""
         st = stream()
         ws, Ws, bufs, B = self.plan.windows, self._W, self.bufs, self.B
         if first:
-            self._reflect(n, 0, st)
+            self._reflect(n, 0, st, slots)
         for i, L in enumerate(self.plan.layers):
             s, d = ws[L.src], ws[L.dst]
             Ws_, Wd = Ws[L.src], Ws[L.dst]
@@ -348,41 +471,72 @@ class _Session:
                      s.C * Ws_, Ws_, d.C * Wd, Wd, ops.ACT[L.act], st)
             else:
                 m = self._lstm[i]
-                call('encx_stream_lstm', bufs[L.src].data_ptr() + 4 * s.P, m['wcatT'].data_ptr(),
-                     m['bsum'].data_ptr(), m['hz'].data_ptr(), m['c'].data_ptr(), m['gates'].data_ptr(), y,
-                     int(bool(L.module.skip)), B, n * s.rate, L.Cin, L.module.lstm.num_layers, s.C * Ws_, Ws_,
-                     d.C * Wd, Wd, st)
+                args = (bufs[L.src].data_ptr() + 4 * s.P, m['wcatT'].data_ptr(),
+                        m['bsum'].data_ptr(), m['hz'].data_ptr(), m['c'].data_ptr(), m['gates'].data_ptr(), y,
+                        int(bool(L.module.skip)), B, n * s.rate, L.Cin, L.module.lstm.num_layers, s.C * Ws_, Ws_,
+                        d.C * Wd, Wd)
+                if slots:
+                    if s.rate != 1:  # the table counts frames, the recurrence columns
+                        _refuse(f'{L.name}: per-slot steps of an LSTM at {s.rate} columns per frame')
+                    call('encx_stream_lstm_slots', *args, self._slots.data_ptr(), st)
+                else:
+                    call('encx_stream_lstm', *args, st)
             if first and L.final:
-                self._reflect(n, L.dst, st)
+                self._reflect(n, L.dst, st, slots)
+        if slots:
+            tab, nfull, rows, _ = self._slot_tab
+            if nfull:
+                call('encx_stream_roll_slots', tab.data_ptr(), nfull, rows, ROLL_SHIFT, self._slots.data_ptr(), B, st)
+            return
         tab, nfull, rows, _ = self._table(n)
         if nfull:
             call('encx_stream_roll', tab.data_ptr(), nfull, rows, 0, st)
 
-    def _step(self, n, body):
-        """Run body(n, first) eagerly, or as the graph captured for (n, first) the first time."""
-        first = not self.started
-        self._table(n)
+    def _run(self, graphs, key, body):
+        """body(*key) eagerly, or as the graph captured for key the first time."""
         if not self.graphs:
-            out = body(n, first)
-        else:
-            ent = self._graphs.get((n, first))
-            if ent is None:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):  # one stream: the graph has no parallel branches
-                    res = body(n, first)
-                ent = self._graphs[(n, first)] = (g, res)
-            ent[0].replay()
-            out = tuple(t.clone() for t in ent[1])  # the graph's outputs are rewritten by its next replay
-        self.started = True
+            return body(*key)
+        ent = graphs.get(key)
+        if ent is None:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):  # one stream: the graph has no parallel branches
+                res = body(*key)
+            ent = graphs[key] = (g, res)
+        ent[0].replay()
+        return tuple(t.clone() for t in ent[1])  # the graph's outputs are rewritten by its next replay
+
+    def _step(self, n, body):
+        """A uniform step (see uniform()): body(n, first), keyed (n, first)."""
+        first = not all(self.started)
+        self._table(n)
+        out = self._run(self._graphs, (n, first), body)
+        self.started = [True] * self.B
+        self._fresh = False
         return out
 
-    def _warm(self, body):
+    def _step_slots(self, frames, n_max, any_first, body):
+        """A step under the slot table (already filled: put_slots): body(n_max, any_first), keyed
+        (n_max, any_first). The table is read by the kernels, so one graph serves whichever slots
+        join, sit out or deliver fewer frames."""
+        out = self._run(self._slot_graphs, (n_max, any_first), body)
+        for b, f in enumerate(frames):
+            if f:
+                self.started[b] = True
+        self._fresh = False
+        return out
+
+    def _warm(self, body, body_slots):
         """Load every kernel of a step before any capture: one first chunk and one later chunk on
-        the zero state, eagerly; then back to a clean session."""
+        the zero state, eagerly, without and with the slot table; then back to a clean session."""
         graphs, self.graphs = self.graphs, False
         try:
             self._step(self.min_first_frames, body)
             self._step(1, body)
+            self.reset()
+            for n in (self.min_first_frames, 1):
+                frames = [n] * self.B
+                self.put_slots(frames)
+                self._step_slots(frames, *self.check_frames(frames), body_slots)
         finally:
             self.graphs = graphs
         self.reset()
@@ -406,7 +560,7 @@ class StreamEncoder:
         self.channels = model.channels
         self._embeds = _embeds(model, self.n_q)
         with torch.no_grad():
-            self._s._warm(self._body)
+            self._s._warm(self._body, self._body_slots)
 
     hop_length = property(lambda self: self._s.hop_length)
     min_first_frames = property(lambda self: self._s.min_first_frames)
@@ -414,6 +568,11 @@ class StreamEncoder:
 
     def reset(self):
         self._s.reset()
+
+    def restart(self, slots):
+        """The named slots (indices 0..batch-1) start a new stream with their next non-empty
+        chunk; the other slots are not disturbed. Legal between any two steps; launches nothing."""
+        self._s.restart(slots)
 
     def refresh_weights(self):
         self._s.refresh_weights()
@@ -427,20 +586,55 @@ class StreamEncoder:
         codes = ops.rvq_encode(emb, self._embeds).permute(1, 0, 2).contiguous()
         return codes, emb
 
-    @torch.no_grad()
-    def encode(self, x: torch.Tensor, return_latent: bool = False):
-        """x [B, C, n * hop_length] float32 on the model's device -> codes [B, n_q, n] (and the
-        latent [B, D, n] with return_latent). Equals the offline model on the audio so far."""
+    def _body_slots(self, n, first):
+        s = self._s
+        s._layers(n, first, slots=True)
+        keep = s.keep(n, 1)
+        # the columns past a slot's count are zero (and a copy, as above)
+        emb = torch.where(keep, s.bufs[s.plan.layers[-1].dst][:, :, :n], 0.).contiguous()
+        codes = torch.where(keep, ops.rvq_encode(emb, self._embeds).permute(1, 0, 2), 0).contiguous()
+        return codes, emb
+
+    def _samples(self, x):
         s = self._s
         if x.dim() != 3 or x.shape[0] != s.B or x.shape[1] != self.channels or x.shape[2] % s.hop_length:
             raise ValueError(f'encx streaming: expected [{s.B}, {self.channels}, n * {s.hop_length}] samples, '
                              f'got {tuple(x.shape)}')
-        n = x.shape[2] // s.hop_length
-        s._check_chunk(n)
+        return x.shape[2] // s.hop_length
+
+    @torch.no_grad()
+    def encode(self, x: torch.Tensor, return_latent: bool = False):
+        """x [B, C, n * hop_length] float32 on the model's device -> codes [B, n_q, n] (and the
+        latent [B, D, n] with return_latent). Equals the offline model on the audio so far. The
+        uniform case of encode_slots: every slot delivers n frames."""
+        s = self._s
+        n = self._samples(x)
+        s.check_frames([n] * s.B)
         ops._check(x)
+        if not s.uniform():  # some slots are on their first chunk, others not
+            return self.encode_slots(x, [n] * s.B, return_latent)
         P = s.plan.windows[0].P
         s.bufs[0][:, :, P:P + x.shape[2]].copy_(x)
         codes, emb = s._step(n, self._body)
+        return (codes, emb) if return_latent else codes
+
+    @torch.no_grad()
+    def encode_slots(self, x: torch.Tensor, frames: tp.Sequence[int], return_latent: bool = False):
+        """x [B, C, n_max * hop_length], frames[b] = the frames slot b delivers (0: it sits out),
+        n_max = max(frames) -> codes [B, n_q, n_max] (and the latent [B, D, n_max]). Slot b's
+        samples past frames[b] * hop_length are not read; its result columns past frames[b] are
+        zero. Each slot equals the same stream alone."""
+        s = self._s
+        n = self._samples(x)
+        frames = _ints(frames, 'frames')
+        n_max, any_first = s.check_frames(frames)
+        if n != n_max:
+            raise ValueError(f'encx streaming: {n} frames of samples for max(frames) = {n_max}')
+        ops._check(x)
+        s.put_slots(frames)
+        P = s.plan.windows[0].P
+        s.bufs[0][:, :, P:P + x.shape[2]].copy_(torch.where(s.keep(x.shape[2], s.hop_length), x, 0.))
+        codes, emb = s._step_slots(frames, n_max, any_first, self._body_slots)
         return (codes, emb) if return_latent else codes
 
 
@@ -459,7 +653,7 @@ class StreamDecoder:
         self._embeds = _embeds(model, self.n_q)
         self._codes: tp.Dict[int, torch.Tensor] = {}
         with torch.no_grad():
-            self._s._warm(self._body)
+            self._s._warm(self._body, self._body_slots)
 
     hop_length = property(lambda self: self._s.hop_length)
     min_first_frames = property(lambda self: self._s.min_first_frames)
@@ -467,6 +661,10 @@ class StreamDecoder:
 
     def reset(self):
         self._s.reset()
+
+    def restart(self, slots):
+        """As StreamEncoder.restart."""
+        self._s.restart(slots)
 
     def refresh_weights(self):
         self._s.refresh_weights()
@@ -488,19 +686,56 @@ class StreamDecoder:
         out = s.bufs[s.plan.layers[-1].dst][:, :, :n * s.hop_length]
         return (out.clone(memory_format=torch.contiguous_format),)
 
-    @torch.no_grad()
-    def decode(self, codes: torch.Tensor) -> torch.Tensor:
-        """codes [B, n_q, n] int64 on the model's device -> wav [B, C, n * hop_length]. Equals
-        the offline decoder on the codes so far. Codes are clamped to the codebook size."""
+    def _body_slots(self, n, first):
+        s = self._s
+        q = ops.rvq_decode(self._code_buf(n), self._embeds)
+        P = s.plan.windows[0].P
+        s.bufs[0][:, :, P:P + n].copy_(q)
+        s._layers(n, first, slots=True)
+        # the samples past a slot's count are zero (and a copy, as above)
+        out = s.bufs[s.plan.layers[-1].dst][:, :, :n * s.hop_length]
+        return (torch.where(s.keep(n * s.hop_length, s.hop_length), out, 0.).contiguous(),)
+
+    def _frames(self, codes):
         s = self._s
         if codes.dim() != 3 or codes.shape[0] != s.B or codes.shape[1] != self.n_q or codes.dtype != torch.int64:
             raise ValueError(f'encx streaming: expected int64 codes [{s.B}, {self.n_q}, n], got '
                              f'{codes.dtype} {tuple(codes.shape)}')
-        n = codes.shape[2]
-        s._check_chunk(n)
+        return codes.shape[2]
+
+    @torch.no_grad()
+    def decode(self, codes: torch.Tensor) -> torch.Tensor:
+        """codes [B, n_q, n] int64 on the model's device -> wav [B, C, n * hop_length]. Equals
+        the offline decoder on the codes so far. Codes are clamped to the codebook size. The
+        uniform case of decode_slots: every slot delivers n frames."""
+        s = self._s
+        n = self._frames(codes)
+        s.check_frames([n] * s.B)
         if not codes.is_cuda:
             raise RuntimeError('encx streaming takes device tensors (no CPU fallback)')
+        if not s.uniform():  # some slots are on their first chunk, others not
+            return self.decode_slots(codes, [n] * s.B)
         buf = self._code_buf(n)
         buf.copy_(codes.permute(1, 0, 2))
         buf.clamp_(0, self.bins - 1)  # an index outside the codebook must never reach the gather
         return s._step(n, self._body)[0]
+
+    @torch.no_grad()
+    def decode_slots(self, codes: torch.Tensor, frames: tp.Sequence[int]) -> torch.Tensor:
+        """codes [B, n_q, n_max], frames[b] = the frames slot b delivers (0: it sits out), n_max =
+        max(frames) -> wav [B, C, n_max * hop_length]. Slot b's codes past frames[b] are not read
+        (code 0 is decoded in their place); its samples past frames[b] * hop_length are zero.
+        Each slot equals the same stream alone."""
+        s = self._s
+        n = self._frames(codes)
+        frames = _ints(frames, 'frames')
+        n_max, any_first = s.check_frames(frames)
+        if n != n_max:
+            raise ValueError(f'encx streaming: {n} frames of codes for max(frames) = {n_max}')
+        if not codes.is_cuda:
+            raise RuntimeError('encx streaming takes device tensors (no CPU fallback)')
+        s.put_slots(frames)
+        buf = self._code_buf(n)
+        # clamped as in decode(); past a slot's count whatever the caller left becomes code 0
+        buf.copy_(torch.where(s.keep(n, 1).squeeze(1), codes.permute(1, 0, 2).clamp(0, self.bins - 1), 0))
+        return s._step_slots(frames, n_max, any_first, self._body_slots)[0]

@@ -781,6 +781,43 @@ typedef struct {
 } encx_stream_win;
 int encx_stream_roll(const encx_stream_win* wins, int64_t n_wins, int64_t rows_total, int reflect,
                      encx_stream_t stream);
+/* Per-slot lifecycle: the streams (slots) of a session join, leave and advance by their own frame
+ * counts. A SLOT TABLE in device memory, int32 slots[2*B], is read by the kernels (so a captured
+ * graph replays for any set of joining slots): slots[2b] = latent frames slot b delivers this step
+ * (0: it sits out), slots[2b+1] = 1 when this is the slot's first chunk. A step computes n_max =
+ * max frames columns for every slot (the convs need no masking: every layer is causal, so the
+ * columns past a slot's count influence nothing that is carried); only the two carriers of state
+ * below look at the table. The kernels are those of encx_stream_roll / encx_stream_lstm, which run
+ * them without a table.
+ *
+ * The roll over a table of encx_stream_slot_win: an encx_stream_win (n_cols is ignored) plus chans,
+ * the window's channel rows per slot (row i belongs to slot i / chans; rows = B * chans), and rate,
+ * its columns per latent frame; a row of slot b moves n_cols = slots[2b] * rate columns.
+ *   ENCX_ROLL_SHIFT    end of a step: [n_cols, n_cols + P) -> [0, P), the row loaded whole before
+ *                      any store; a slot with 0 frames keeps its history.
+ *   ENCX_ROLL_REFLECT  rows of slots on their first chunk (with frames > 0): column c <- 2P - c.
+ *   ENCX_ROLL_ZERO     rows of slots on their first chunk: columns [0, P) <- 0 (the transposed
+ *                      conv's previous column).
+ * A row whose table values would leave the row (n_cols + P > rstride; reflect: n_cols <= P) is
+ * skipped, never addressed outside [0, rstride). B <= 64, P <= 64. */
+#define ENCX_ROLL_SHIFT 0
+#define ENCX_ROLL_REFLECT 1
+#define ENCX_ROLL_ZERO 2
+typedef struct {
+    float* ptr;
+    int64_t rows, P, n_cols, rstride, row0; /* as encx_stream_win */
+    int64_t chans, rate;
+} encx_stream_slot_win;
+int encx_stream_roll_slots(const encx_stream_slot_win* wins, int64_t n_wins, int64_t rows_total, int mode,
+                           const int32_t* slots, int64_t B, encx_stream_t stream);
+/* encx_stream_lstm for t < n_max with the slot table: for t >= slots[2b] slot b's c, the h halves
+ * of hz and its output column t are left as they are; a slot on its first chunk takes h (every
+ * layer) and c as 0 at t = 0 instead of what hz / c hold. The gate GEMM runs over all B rows (they
+ * are independent). Launches as encx_stream_lstm: 1 + 2L per frame. */
+int encx_stream_lstm_slots(const float* x, const float* wcatT, const float* bsum, float* hz, float* c, float* gates,
+                           float* out, int skip, int64_t B, int64_t n_max, int64_t H, int64_t L, int64_t x_bstride,
+                           int64_t x_rstride, int64_t out_bstride, int64_t out_rstride, const int32_t* slots,
+                           encx_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,12 @@ events around blocks of steps, >= 0.3 s per variant, 5 rounds after a warm-up; m
 rounds' min / max. `real_time` is the one derived condition: at B = 64, n = 1 an encode step plus
 a decode step (graph replay) must take less than the frame period, 1000 / 75 = 13.33 ms.
 
+--slots measures the per-slot entry points instead (encode_slots / decode_slots / restart, see
+slots_section) and writes profiles/stream/stream_bench_slots.json; there the real-time condition
+is the join step's encode plus decode against the frame period.
+
 python tools/stream_bench.py [--batches 1,16,64] [--frames 1,4] [--rounds 5] [--out FILE]
+python tools/stream_bench.py --slots [--rounds 5] [--slots-out FILE]
 """
 import argparse
 import json
@@ -31,8 +36,66 @@ def stats(ms):
     return {'ms': round(statistics.median(ms), 4), 'min': round(min(ms), 4), 'max': round(max(ms), 4)}
 
 
+def slots_section(args, torch, m, dev, hop, period_ms, measure, B=64, join=7):
+    """Per-slot steps at B = 64 (graph replay), one session pair for all of it:
+      sustained   every slot delivers 1 frame through encode_slots / decode_slots, against the
+                  same through encode / decode (the slot table does not change: no upload);
+      join        63 slots deliver 1 frame and one slot, restarted just before, its first 7; the
+                  joining slot moves on by one every step, so every step uploads a new table;
+      uniform     every slot delivers 7 frames through encode / decode: the join step computes
+                  the same columns, so this is what it should cost."""
+    from encx.streaming import StreamEncoder, StreamDecoder
+    g = torch.Generator().manual_seed(6400)
+    noise = lambda n: (0.1 * torch.randn(B, 1, n * hop, generator=g)).to(dev)
+    enc = StreamEncoder(m, B)
+    dec = StreamDecoder(m, B, enc.n_q)
+    x1, x7 = noise(1), noise(join)
+    ones = [1] * B
+    c7 = enc.encode(x7)
+    dec.decode(c7)
+    c1 = enc.encode(x1)
+    joins = [[join if b == j else 1 for b in range(B)] for j in range(B)]
+    turn = {'enc': 0, 'dec': 0}
+
+    def join_step(side, obj, fn, arg):
+        j = turn[side] = (turn[side] + 1) % B
+        obj.restart([j])
+        fn(arg, joins[j])
+
+    res = {}
+    for key, fn in (('sustained_encode_slots', lambda: enc.encode_slots(x1, ones)),
+                    ('sustained_encode', lambda: enc.encode(x1)),
+                    ('sustained_decode_slots', lambda: dec.decode_slots(c1, ones)),
+                    ('sustained_decode', lambda: dec.decode(c1)),
+                    ('join_encode', lambda: join_step('enc', enc, enc.encode_slots, x7)),
+                    ('uniform7_encode', lambda: enc.encode(x7)),
+                    ('join_decode', lambda: join_step('dec', dec, dec.decode_slots, c7)),
+                    ('uniform7_decode', lambda: dec.decode(c7))):
+        res[key], _ = measure(fn)
+        print(json.dumps({key: res[key]}), flush=True)
+    ms = lambda k: res[k]['ms']
+    join_ms = ms('join_encode') + ms('join_decode')
+    return {'metric': f'ms per streaming step at B = {B} (graph replay), per-slot entry points',
+            'device': torch.cuda.get_device_name(0), 'model': 'causal 24 kHz SEANet, random weights, n_q 8',
+            'frame_period_ms': round(period_ms, 4), 'rounds': args.rounds,
+            'timing': f'device events around blocks of steps, >= {args.min_seconds} s per variant, after warm-up',
+            'steps': res,
+            'sustained_slots_over_uniform': {s: round(ms(f'sustained_{s}_slots') / ms(f'sustained_{s}'), 4)
+                                             for s in ('encode', 'decode')},
+            'join_over_uniform7': {'encode': round(ms('join_encode') / ms('uniform7_encode'), 4),
+                                   'decode': round(ms('join_decode') / ms('uniform7_decode'), 4),
+                                   'encode_plus_decode': round(
+                                       join_ms / (ms('uniform7_encode') + ms('uniform7_decode')), 4)},
+            'real_time': {'B': B, 'step': f'join: 63 slots x 1 frame, one slot its first {join}',
+                          'encode_plus_decode_graph_ms': round(join_ms, 4),
+                          'frame_period_ms': round(period_ms, 4), 'met': join_ms < period_ms}}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--slots', action='store_true', help='only the per-slot section (B = 64)')
+    ap.add_argument('--slots-out', type=str,
+                    default=os.path.join(ROOT, 'profiles', 'stream', 'stream_bench_slots.json'))
     ap.add_argument('--batches', type=str, default='1,16,64')
     ap.add_argument('--frames', type=str, default='1,4')
     ap.add_argument('--rounds', type=int, default=5)
@@ -72,6 +135,16 @@ def main():
         torch.cuda.synchronize()
         iters = max(5, int(args.min_seconds * 1e3 / args.rounds / max(timed(fn, 5), 1e-3)) + 1)
         return stats([timed(fn, iters) for _ in range(args.rounds)]), iters
+
+    if args.slots:
+        with torch.no_grad():
+            res = slots_section(args, torch, m, dev, hop, period_ms, measure)
+        print(json.dumps(res), flush=True)
+        if args.slots_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.slots_out)), exist_ok=True)
+            with open(args.slots_out, 'w') as f:
+                f.write(json.dumps(res, indent=1) + '\n')
+        return
 
     rows = []
     with torch.no_grad():
