@@ -99,3 +99,41 @@ ENCX_DEV f32x4 quad_abs(f32x4 v, int o, int last) {
 // -- the workgroup-major order piled it onto the first CUs, costing a whole extra round on layers
 // with 1.5x or 2.9x as many items as wave slots -- and neighbouring items still share an XCD's L2.
 ENCX_DEV int rw_first_slot(int wave) { return wave * (int)gridDim.x + xcd_linear_id(); }
+
+// Staging quads in flight per thread of the register-window kernels' weight copy: every load of a
+// thread is issued before its first LDS write (15 quads cover the 120 KB of the 3x9 layers at 512
+// threads; the registers are free before the first item).
+constexpr int RW_SQ = 15;
+
+// Development tracing of the register-window forward / bwd-data kernels (build with
+// -DENCX_C2_TRACE: `make trace`; tools/c2_trace.py reads it). Lane 0 of every wave stamps the
+// steady clock (100 MHz) into the buffer given to encx_conv2d_trace, C2_TR_W int64 per wave
+// (wave = block * NWV + wave in block): [0] kernel entry, [1] after the staging barrier, [2] items
+// done, then per item [3 + 3 i ..] main-loop start, main-loop end, epilogue end.
+constexpr int C2_TR_W = 32, C2_TR_ITEMS = (C2_TR_W - 3) / 3;
+struct C2Trace {
+    long long* buf;
+    int waves;  // capacity of buf in waves
+};
+#ifdef ENCX_C2_TRACE
+extern C2Trace g_c2_trace;
+#define C2_TRACE_ARG C2Trace tr;
+#define C2_TRACE_SET(s) (s).tr = g_c2_trace
+#define C2_TRACE_VAL(tr, slot, k, v)                                                     \
+    do {                                                                                 \
+        if ((tr).buf && (threadIdx.x & 63) == 0 && (slot) < (tr).waves && (k) < C2_TR_W) \
+            (tr).buf[(int64_t)(slot) * C2_TR_W + (k)] = (long long)(v);                  \
+    } while (0)
+#define C2_TRACE(tr, slot, k) C2_TRACE_VAL(tr, slot, k, wall_clock64())
+#else
+#define C2_TRACE_ARG
+#define C2_TRACE_SET(s) \
+    do {                \
+    } while (0)
+#define C2_TRACE_VAL(tr, slot, k, v) \
+    do {                             \
+    } while (0)
+#define C2_TRACE(tr, slot, k) \
+    do {                      \
+    } while (0)
+#endif

@@ -525,6 +525,7 @@ struct C2DgR {
     C2Dg d;
     int U4;     // quads per polyphase row
     int tiles;  // column tiles (32 quads each): ceil(B * T2 * U4 / 32)
+    C2_TRACE_ARG
 };
 // c2_dgrad_rw_kernel's epilogue for one item, the combination of its terms fixed at compile time
 // (MODE bits: 1 feature term, 2 LeakyReLU'(x), 4 x read from xact (else from ffx), 8 accumulate),
@@ -560,39 +561,57 @@ ENCX_DEV void rw_dg_epi(const C2Dg& a, const f32x16 (&acc)[TM][4], int rt, int l
         const int f = 2 * u0 - g.pf;
         const bool inb = f >= 0 && f + 8 <= g.Fi;
         if constexpr (PS && C && !LX && !F && !A) {
-            // the premasked feature-code epilogue (the map's only input is its 1-byte code): the
-            // codes of four row pairs as unaligned dwords (8 bytes per row, two loads) issued
-            // together, then combined and stored; one round trip per four pairs instead of one
-            // per pair of 16 byte loads
-            if (inb) {
+            // the premasked feature-code epilogue (the map's only input is its 1-byte code), for
+            // EVERY lane, the ones at a row's edges included: a tile of 32 quads spans a row edge in
+            // nearly every wave (33 quads per row at F 257), and such a wave then also ran the
+            // per-element path below for its edge lanes, eight chunks of byte loads, a wait and
+            // scalar stores each: 84 us per item against the plain epilogue's 19 at T 184 / F 257
+            // (profiles/c2_items). Here the codes of a half quad are one unaligned dword loaded from
+            // min(max(column, 0), Fi - 4), inside the row, and shifted into place (the bytes of
+            // columns outside the row fall out or are never stored); four row pairs' loads are
+            // issued together, then combined and stored: quads where the half lies inside the row,
+            // single elements at the edges. The rows of a lane are row_stride apart.
+            {
                 typedef uint32_t u32u __attribute__((aligned(1)));
+                const int64_t orow = (((int64_t)b * g.Ci + mfma_row(0, lane)) * g.T2 + t) * g.Fi;
+                const int64_t row_stride = (int64_t)g.T2 * g.Fi;
+                int cl[2], sh[2];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    cl[h] = min(max(f + 4 * h, 0), g.Fi - 4);
+                    sh[h] = f + 4 * h - cl[h];  // 0: the half lies inside the row
+                }
 #pragma unroll
                 for (int hb = 0; hb < 16; hb += 4 * EP) {
-                    uint32_t cw[4][EP][2];
-                    int64_t oo[4][EP];
+                    uint32_t cw[4 * EP][2];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j)
+                    for (int j = 0; j < 4 * EP; ++j)
 #pragma unroll
-                        for (int p = 0; p < EP; ++p) {
-                            const int ci = mfma_row(hb + j * EP + p, lane);
-                            oo[j][p] = (((int64_t)b * g.Ci + ci) * g.T2 + t) * g.Fi + f;
-                            cw[j][p][0] = *(const u32u*)(cs + oo[j][p]);
-                            cw[j][p][1] = *(const u32u*)(cs + oo[j][p] + 4);
-                        }
+                        for (int h = 0; h < 2; ++h)
+                            cw[j][h] = *(const u32u*)(cs + orow + (mfma_row(hb + j, 0) - mfma_row(0, 0)) * row_stride + cl[h]);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j)
+                    for (int j = 0; j < 4 * EP; ++j)
 #pragma unroll
-                        for (int p = 0; p < EP; ++p)
+                        for (int h = 0; h < 2; ++h) {
+                            const int r = hb + j, n = sh[h];
+                            const uint32_t c4 = n == 0 ? cw[j][h]
+                                                : n > 0 ? (n < 4 ? cw[j][h] >> (8 * n) : 0u)
+                                                        : (n > -4 ? cw[j][h] << (-8 * n) : 0u);
+                            f32x4 s4;
 #pragma unroll
-                            for (int h = 0; h < 2; ++h) {
-                                f32x4 s4;
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) {
-                                    const int e8 = 4 * h + e, r = hb + j * EP + p;
-                                    s4[e] = combine(acc[e8 & 1][e8 >> 1][r], 0.f, 0.f, 0.f, (cw[j][p][h] >> (8 * e)) & 255u);
-                                }
-                                *(f32x4u*)(dx + oo[j][p] + 4 * h) = s4;
+                            for (int e = 0; e < 4; ++e) {
+                                const int e8 = 4 * h + e;
+                                s4[e] = combine(acc[e8 & 1][e8 >> 1][r], 0.f, 0.f, 0.f, (c4 >> (8 * e)) & 255u);
                             }
+                            float* dr = dx + orow + (mfma_row(r, 0) - mfma_row(0, 0)) * row_stride + f + 4 * h;
+                            if (n == 0) {
+                                *(f32x4u*)dr = s4;
+                            } else {
+#pragma unroll
+                                for (int e = 0; e < 4; ++e)
+                                    if (f + 4 * h + e >= 0 && f + 4 * h + e < g.Fi) dr[e] = s4[e];
+                            }
+                        }
                 }
                 return;
             }
@@ -708,20 +727,15 @@ __global__ __launch_bounds__(NWV * 64) void c2_dgrad_rw_kernel(C2DgR R) {
     const C2Dg& a = R.d;
     extern __shared__ float smem[];
     const C2Geo g = a.g;
+    const int tslot = blockIdx.x * NWV + (threadIdx.x >> 6);  // (trace builds only)
+    int titem = 0;
+    (void)titem;
+    C2_TRACE(R.tr, tslot, 0);
     // phase-split rows (the 3x9 stride-2 layers with both row tiles per item): tile 0 = phase 0,
     // tile 1 = phase 1 of the 32 ci, so the fifth polyphase tap, zero for every phase-1 row
     // (kf = 2 q + 1 = 9 >= KF), is skipped for tile 1: 10 % fewer MFMAs
     constexpr bool PS = S == 2 && J == 5 && RT == 2 && TM == 2;
     float* As = smem;  // [(co,kt)][J][M]: the wp layout (M == Ci*S, host-checked), rows phase-major if PS
-    for (int i = threadIdx.x; i < g.Co * KT * J * M; i += NWV * 64) {
-        if (PS) {
-            const int mn = i % M;
-            As[i] = a.wp[i - mn + (mn & 31) * S + (mn >> 5)];
-        } else {
-            As[i] = a.wp[i];
-        }
-    }
-    __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, l = lane & 31;
     // element offsets fit in 32 bits (checked on the host)
     const int quads = g.B * g.T2 * R.U4;
@@ -777,7 +791,35 @@ __global__ __launch_bounds__(NWV * 64) void c2_dgrad_rw_kernel(C2DgR R) {
     };
     const int stride = gridDim.x * NWV, nitems = R.tiles * RG;
     int item = rw_first_slot(wave);
+    // the first item's window goes out ahead of the weights, so it arrives under their staging
     if (item < nitems) load(0, geo(item), 0, 0);
+    // the weights, once per workgroup: wp copied as quads, RW_SQ of them in flight per thread ahead
+    // of their LDS writes (one memory round trip for the 3x9 layers' 120 KB at 512 threads; loaded
+    // dword by dword, eight in flight, it was eight). Phase-split rows: the quad (ci, 0), (ci, 1),
+    // (ci + 1, 0), (ci + 1, 1) of wp goes to columns ci, ci + 1 of tile 0 and of tile 1.
+    {
+        const int nq = g.Co * KT * J * (M / 4);
+        for (int i0 = 0; i0 < nq; i0 += NWV * 64 * RW_SQ) {
+            f32x4 sv[RW_SQ];
+#pragma unroll
+            for (int u = 0; u < RW_SQ; ++u)
+                sv[u] = ld4u(a.wp + 4 * min(i0 + u * NWV * 64 + (int)threadIdx.x, nq - 1));
+#pragma unroll
+            for (int u = 0; u < RW_SQ; ++u) {
+                const int i = i0 + u * NWV * 64 + (int)threadIdx.x;
+                if (i >= nq) continue;
+                if (PS) {
+                    const int col = (4 * i) % M, ci = col >> 1;
+                    *(f32x2*)(As + 4 * i - col + ci) = (f32x2){sv[u][0], sv[u][2]};
+                    *(f32x2*)(As + 4 * i - col + 32 + ci) = (f32x2){sv[u][1], sv[u][3]};
+                } else {
+                    *(f32x4*)(As + 4 * i) = sv[u];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    C2_TRACE(R.tr, tslot, 1);
     for (; item < nitems; item += stride) {
         const Geo cur = geo(item);  // (recomputed: cheaper than holding the next item's in registers)
         const int rt = cur.rt, tile = cur.tile, t = cur.t, b = cur.b, u0 = cur.u0;
@@ -787,6 +829,7 @@ __global__ __launch_bounds__(NWV * 64) void c2_dgrad_rw_kernel(C2DgR R) {
         for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = (f32x16){0};
+        C2_TRACE(R.tr, tslot, 3 + 3 * titem);
         for (int c0 = 0; c0 < CP; c0 += 2) {
 #pragma unroll
             for (int u = 0; u < 2 * KT; ++u) {
@@ -835,6 +878,7 @@ __global__ __launch_bounds__(NWV * 64) void c2_dgrad_rw_kernel(C2DgR R) {
                 }
             }
         }
+        C2_TRACE(R.tr, tslot, 4 + 3 * titem);
         // ---- epilogue (rw_dg_epi): the feature-matching term, LeakyReLU'(x), accumulate
         const bool live = tile * 32 + l < quads;
         const bool ldx = a.xact && !(a.ffr && a.ffx == a.xact);  // x from xact (else from ffx)
@@ -849,6 +893,9 @@ __global__ __launch_bounds__(NWV * 64) void c2_dgrad_rw_kernel(C2DgR R) {
 #undef ENCX_EPI
             default: break;  // (xact without its own load needs ffr: modes 2, 10 do not occur)
         }
+        C2_TRACE(R.tr, tslot, 5 + 3 * titem);
+        ++titem;
+        C2_TRACE_VAL(R.tr, tslot, 2, titem);
     }
 }
 
@@ -1109,6 +1156,7 @@ static int run_dgrad_rw(const C2Dg& d, int wgs, hipStream_t st) {
     const size_t lds = (size_t)g.Co * 3 * J * g.Ci * g.sf * sizeof(float);
     const int grid = (int)min((int64_t)wgs, cdiv((int64_t)tiles, NWV));
     R.tiles = tiles;
+    C2_TRACE_SET(R);
     launch_dgrad_rw(R, grid, lds, st);
     ENCX_CHECK_LAUNCH();
     return 0;

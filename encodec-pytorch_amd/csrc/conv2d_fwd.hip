@@ -343,20 +343,19 @@ struct C2FwdR {
     int act;
     int F4;     // quads per output row
     int tiles;  // ceil(B * T2 * F4 / 32)
+    C2_TRACE_ARG
 };
 template <int KF, int S, int WQ, int NWV>
 __global__ __launch_bounds__(NWV * 64) void c2_fwd_rw_kernel(C2FwdR a) {
     constexpr int NE = 4 * WQ, KT = 3;  // window elements per lane; kernel rows (host-checked)
     extern __shared__ float smem[];
     const C2Geo g = a.g;
+    const int tslot = blockIdx.x * NWV + (threadIdx.x >> 6);  // (trace builds only)
+    int titem = 0;
+    (void)titem;
+    C2_TRACE(a.tr, tslot, 0);
     float* Ws = smem;                          // [Ci*KT][KF][32]
     float* Bs = smem + g.Ci * KT * KF * 32;    // [32] bias
-    for (int i = threadIdx.x; i < g.Ci * KT * KF * 32; i += NWV * 64) {
-        const int co = i & 31, r = i >> 5;
-        Ws[i] = co < g.Co ? a.wf[r * g.Co + co] : 0.f;
-    }
-    if (threadIdx.x < 32) Bs[threadIdx.x] = (a.bias && (int)threadIdx.x < g.Co) ? a.bias[threadIdx.x] : 0.f;
-    __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, l = lane & 31;
     // element offsets fit in 32 bits (checked on the host)
     const int quads = g.B * g.T2 * a.F4;
@@ -409,13 +408,41 @@ __global__ __launch_bounds__(NWV * 64) void c2_fwd_rw_kernel(C2FwdR a) {
     auto wcol = [&](int c, int kt) { return Ws + ((2 * c + h) * KT + kt) * KF * 32 + l; };
     const int stride = gridDim.x * NWV;
     int tile = rw_first_slot(wave);
+    // the first item's window goes out ahead of the weights, so it arrives under their staging
     if (tile < a.tiles) load(wb[0], geo(tile), 0, 0);
+    // the weights, once per workgroup. Co == 32 (every layer of the discriminator): wf is the LDS
+    // layout, copied as quads, RW_SQ of them in flight per thread ahead of their LDS writes (one
+    // memory round trip for the 32-channel layers' 108 KB at 512 threads; loaded dword by dword,
+    // eight in flight, it was seven).
+    if (g.Co == 32) {
+        const int nq = g.Ci * KT * KF * 8;
+        for (int i0 = 0; i0 < nq; i0 += NWV * 64 * RW_SQ) {
+            f32x4 sv[RW_SQ];
+#pragma unroll
+            for (int u = 0; u < RW_SQ; ++u)
+                sv[u] = ld4u(a.wf + 4 * min(i0 + u * NWV * 64 + (int)threadIdx.x, nq - 1));
+#pragma unroll
+            for (int u = 0; u < RW_SQ; ++u) {
+                const int i = i0 + u * NWV * 64 + (int)threadIdx.x;
+                if (i < nq) *(f32x4*)(Ws + 4 * i) = sv[u];
+            }
+        }
+    } else {
+        for (int i = threadIdx.x; i < g.Ci * KT * KF * 32; i += NWV * 64) {
+            const int co = i & 31, r = i >> 5;
+            Ws[i] = co < g.Co ? a.wf[r * g.Co + co] : 0.f;
+        }
+    }
+    if (threadIdx.x < 32) Bs[threadIdx.x] = (a.bias && (int)threadIdx.x < g.Co) ? a.bias[threadIdx.x] : 0.f;
+    __syncthreads();
+    C2_TRACE(a.tr, tslot, 1);
     for (; tile < a.tiles; tile += stride) {
         const Geo cur = geo(tile);  // (recomputed: cheaper than holding the next item's in registers)
         const int t = cur.t, b = cur.b, f0 = cur.f0;
         f32x16 acc[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[j] = (f32x16){0};
+        C2_TRACE(a.tr, tslot, 3 + 3 * titem);
         for (int c = 0; c < CP; ++c) {
 #pragma unroll
             for (int kt = 0; kt < KT; ++kt) {
@@ -447,6 +474,7 @@ __global__ __launch_bounds__(NWV * 64) void c2_fwd_rw_kernel(C2FwdR a) {
                 }
             }
         }
+        C2_TRACE(a.tr, tslot, 4 + 3 * titem);
         // ---- epilogue: rows co, columns f0 + j of this lane's quad
         if (tile * 32 + l < quads) {
 #pragma unroll
@@ -470,6 +498,9 @@ __global__ __launch_bounds__(NWV * 64) void c2_fwd_rw_kernel(C2FwdR a) {
                 }
             }
         }
+        C2_TRACE(a.tr, tslot, 5 + 3 * titem);
+        ++titem;
+        C2_TRACE_VAL(a.tr, tslot, 2, titem);
     }
 }
 
@@ -557,6 +588,7 @@ static int run_fwd_rw(const C2Fwd& f, int wgs, hipStream_t st) {
     const C2Geo& g = f.g;
     C2FwdR a{g, f.x, f.wf, f.bias, f.y, f.act, (int)cdiv(g.Fo, 4), 0};
     a.tiles = (int)cdiv((int64_t)g.B * g.T2 * a.F4, 32);
+    C2_TRACE_SET(a);
     const size_t lds = ((size_t)g.Ci * g.KT * g.KF * 32 + 32) * sizeof(float);
     const int grid = (int)min((int64_t)wgs, cdiv(a.tiles, NWV));
     if (g.KF == 9 && g.sf == 2)
@@ -606,7 +638,23 @@ bool rw_pays(int64_t items, int64_t positions, double ratio) {
     return rounds < ratio * tiled;
 }
 
+#ifdef ENCX_C2_TRACE
+C2Trace g_c2_trace{nullptr, 0};
+#endif
+
 extern "C" {
+
+int encx_conv2d_trace(int64_t* buf, int64_t n) {
+#ifdef ENCX_C2_TRACE
+    ENCX_REQUIRE(n >= 0 && (buf || n == 0));
+    g_c2_trace = C2Trace{(long long*)buf, (int)std::min<int64_t>(n / C2_TR_W, 1 << 20)};
+    return 0;
+#else
+    (void)buf;
+    (void)n;
+    return ENCX_EINVAL;
+#endif
+}
 
 int encx_conv2d_select(int mode) {
     const int prev = g_c2_select;

@@ -467,6 +467,13 @@ int encx_conv2d_bwd_weight(const float* dy, const float* yact, const float* x, f
  * returns the previous setting (any other value only queries). The results of the families agree
  * to fp32 rounding (different summation orders), so tests exercise each at every size. */
 int encx_conv2d_select(int mode);
+/* Development: clock stamps of the register-window forward / bwd-data kernels (steady clock, 100
+ * MHz). buf: device memory of n int64 the caller zeroed, 32 per wave (wave = workgroup * 8 + wave
+ * in workgroup): [0] kernel entry, [1] after the weight-staging barrier, [2] items done, then per
+ * item main-loop start, main-loop end, epilogue end. Every later launch of those kernels writes it
+ * until buf = NULL, n = 0 is set; the caller synchronises before reading. EINVAL unless the
+ * library was built with -DENCX_C2_TRACE (tools/c2_trace.py). */
+int encx_conv2d_trace(int64_t* buf, int64_t n);
 /* Spectrogram(n_fft, hop, win=n_fft, hann, normalized=True, center=False, power=None) of
  * x [B][C][T], written as cat([re, im], 1) in 'b c t w' layout: z [B][2C][Fr][n/2+1]
  * (msstftd.py:97-99). tables: the mel-table buffer of this n_fft (encx_mel_tables_init). */

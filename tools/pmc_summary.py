@@ -1,7 +1,11 @@
 """Summarise rocprofv3 --pmc CSVs per kernel (last timed step of a bench run):
 python tools/pmc_summary.py gpurun_out/pmc1 [gpurun_out/pmc2 ...]
 FETCH_SIZE is doubled for every kernel: on gfx950 it reports half the bytes read for 16-B aligned,
-16-B unaligned, 8-B and 4-B loads alike (tools/mb/fetch_calib.hip, profiles/r05/fetch_calibration.md)."""
+16-B unaligned, 8-B and 4-B loads alike (tools/mb/fetch_calib.hip, profiles/r05/fetch_calibration.md).
+The `vgpr (rocprof)` column is the dispatch record's VGPR_Count + Accum_VGPR_Count as rocprofv3
+writes them, NOT the kernel's register allocation: it showed 128 / 124 / 92 for kernels the compiler
+builds with 253 / 248 / 183 VGPRs. Take register counts and occupancy from the compiler
+(hipcc -Rpass-analysis=kernel-resource-usage; profiles/c2_items/resource_usage.txt)."""
 import collections
 import csv
 import os
@@ -38,7 +42,7 @@ def main():
                 if not c.startswith('_'):
                     per[k][c] += x
     rows = sorted(per.items(), key=lambda kv: -kv[1]["_ns"])[:int(os.environ.get("PMC_TOP", "28"))]
-    print('| kernel | calls | us/call | mfma busy | wait any | wait inst | lds conf | vgpr | lds B | fetch MB/call | '
+    print('| kernel | calls | us/call | mfma busy | wait any | wait inst | lds conf | vgpr (rocprof) | lds B | fetch MB/call | '
           'write MB/call | HBM GB/s |')
     print("|---|---|---|---|---|---|---|---|---|---|---|---|")
     for k, v in rows:
