@@ -18,6 +18,9 @@
 //   codebook entries in parallel for the one interval containing `current`. The intervals are
 //   disjoint and ordered, so this finds exactly the symbol the reference's binary search finds,
 //   and finds none exactly when that search fails (ac.py:238).
+// * encx_ac_encode_slots / encx_ac_decode_slots: the same two coders for the packets of a
+//   streaming step (encx.h): one flushed run per delivering slot, the count from the device slot
+//   table; the decoder starts a new run at step 0 of a slot's packet.
 #include "common.h"
 
 // No mul+add contraction anywhere in this file: the same quantity computed by two kernels (e.g.
@@ -151,13 +154,11 @@ ENCX_DEV int hibit128(u128 x) {  // index of the highest set bit, -1 for 0
     return h ? 127 - __builtin_clzll(h) : (l ? 63 - __builtin_clzll(l) : -1);
 }
 
-__global__ void ac_encode_kernel(const int32_t* __restrict__ lohi, int64_t n, int S, int bits,
-                                 uint8_t* __restrict__ out, int64_t cap, int64_t* __restrict__ nbytes,
-                                 int* __restrict__ err) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= S) return;
-    const int32_t* lh = lohi + (int64_t)s * n * 2;
-    BitOut bo{out + (int64_t)s * cap, cap, 0, 0ull, 0};
+// One coder run: push the n intervals of lh in order, flush, -> the error code of encx_ac_encode;
+// *size = the bytes of the run (those past cap are counted, not written).
+ENCX_DEV int ac_encode_run(const int32_t* __restrict__ lh, int64_t n, int bits, uint8_t* __restrict__ out,
+                           int64_t cap, int64_t* size) {
+    BitOut bo{out, cap, 0, 0ull, 0};
     const uint64_t R = 1ull << bits;
     u128 low = 0, high = 0;
     int max_bit = -1, e = 0;
@@ -207,8 +208,40 @@ __global__ void ac_encode_kernel(const int32_t* __restrict__ lohi, int64_t n, in
         }
         if (bo.pos > cap) e = 2;
     }
-    nbytes[s] = bo.pos;
-    err[s] = e;
+    *size = bo.pos;
+    return e;
+}
+
+__global__ void ac_encode_kernel(const int32_t* __restrict__ lohi, int64_t n, int S, int bits,
+                                 uint8_t* __restrict__ out, int64_t cap, int64_t* __restrict__ nbytes,
+                                 int* __restrict__ err) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    int64_t size;
+    err[s] = ac_encode_run(lohi + (int64_t)s * n * 2, n, bits, out + (int64_t)s * cap, cap, &size);
+    nbytes[s] = size;
+}
+
+// One packet per slot of a streaming step (encx.h): slot b pushes the first frames * K intervals
+// of its n_max * K, flushes, and writes [frames | payload] at out + b * stride. The count comes
+// from the slot table, clamped to 0..n_max; a slot that sits out writes nothing, nbytes 0.
+__global__ void ac_encode_slots_kernel(const int32_t* __restrict__ lohi, int B, int n_max, int K,
+                                       const int32_t* __restrict__ slots, int bits, uint8_t* __restrict__ out,
+                                       int64_t stride, int64_t* __restrict__ nbytes, int* __restrict__ err) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int frames = slots[2 * b];
+    frames = frames < 0 ? 0 : (frames > n_max ? n_max : frames);
+    if (!frames) {
+        nbytes[b] = 0;
+        err[b] = 0;
+        return;
+    }
+    uint8_t* o = out + (int64_t)b * stride;
+    o[0] = (uint8_t)frames;
+    int64_t size;
+    err[b] = ac_encode_run(lohi + (int64_t)b * n_max * K * 2, (int64_t)frames * K, bits, o + 1, stride - 1, &size);
+    nbytes[b] = 1 + size;
 }
 
 // decoder state per stream (ENCX_AC_STATE int64 words): low, high, current (128 bits each,
@@ -217,7 +250,8 @@ __global__ __launch_bounds__(64) void ac_decode_kernel(
     const uint8_t* __restrict__ data, int64_t stride, const int64_t* __restrict__ nbytes,
     int64_t* __restrict__ state, const int32_t* __restrict__ cdf, int K, int card, int bits,
     int64_t* __restrict__ codes, int64_t c_s, int64_t c_k, int64_t c_t, int64_t t,
-    const int64_t* __restrict__ dstep, int64_t* __restrict__ next_idx, int* __restrict__ err) {
+    const int64_t* __restrict__ dstep, int64_t* __restrict__ next_idx, int* __restrict__ err,
+    const int32_t* __restrict__ slots, int n_max) {
     const int s = blockIdx.x, lane = threadIdx.x;
     if (err[s]) return;  // the stream already failed; later steps leave it as it is
     if (dstep) t += *dstep;
@@ -226,6 +260,15 @@ __global__ __launch_bounds__(64) void ac_decode_kernel(
     u128 low = ld128(0), high = ld128(1), cur = ld128(2);
     int max_bit = (int)stt[6];
     int64_t pos = stt[7];
+    if (slots) {  // encx_ac_decode_slots: step t of the slot's packet, a new coder run at t = 0
+        const int frames = slots[2 * s];
+        if (t < 0 || t >= n_max || t >= frames) return;
+        if (t == 0) {
+            low = high = cur = 0;
+            max_bit = -1;
+            pos = 0;
+        }
+    }
     const int64_t nbits = nbytes[s] * 8;
     const uint8_t* src = data + (int64_t)s * stride;
     const uint64_t R = 1ull << bits;
@@ -399,7 +442,33 @@ int encx_ac_decode(const uint8_t* data, int64_t stride, const int64_t* nbytes, i
     ENCX_REQUIRE(data && nbytes && state && cdf && err && streams <= INT32_MAX && K <= INT32_MAX);
     hipLaunchKernelGGL(ac_decode_kernel, dim3((unsigned)streams), dim3(64), 0, (hipStream_t)stream, data, stride,
                        nbytes, state, cdf, (int)K, (int)card, total_range_bits, codes, c_s, c_k, c_t, t, dev_step,
-                       next_idx, err);
+                       next_idx, err, nullptr, 0);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
+
+int encx_ac_encode_slots(const int32_t* lohi, int64_t B, int64_t n_max, int64_t K, const int32_t* slots,
+                         int total_range_bits, uint8_t* out, int64_t out_stride, int64_t* nbytes, int* err,
+                         encx_stream_t stream) {
+    ENCX_REQUIRE(lohi && slots && out && nbytes && err);
+    ENCX_REQUIRE(B >= 1 && B <= 64 && K >= 1 && K <= 64 && n_max >= 1 && n_max <= 255);
+    ENCX_REQUIRE(total_range_bits >= 1 && total_range_bits <= 30 && out_stride >= 1);
+    hipLaunchKernelGGL(ac_encode_slots_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, lohi, (int)B, (int)n_max,
+                       (int)K, slots, total_range_bits, out, out_stride, nbytes, err);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
+
+int encx_ac_decode_slots(const uint8_t* data, int64_t stride, const int64_t* nbytes, int64_t B, int64_t* state,
+                         const int32_t* cdf, int64_t K, int64_t card, int total_range_bits, int64_t* codes,
+                         int64_t c_s, int64_t c_k, int64_t c_t, int64_t n_max, const int64_t* dev_step,
+                         const int32_t* slots, int64_t* prev, int* err, encx_stream_t stream) {
+    ENCX_REQUIRE(data && nbytes && state && cdf && codes && dev_step && slots && prev && err);
+    ENCX_REQUIRE(B >= 1 && B <= 64 && K >= 1 && K <= 64 && n_max >= 1 && n_max <= 255 && stride >= 1);
+    ENCX_REQUIRE(card >= 1 && card <= INT32_MAX && total_range_bits >= 1 && total_range_bits <= 30);
+    hipLaunchKernelGGL(ac_decode_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, data, stride, nbytes,
+                       state, cdf, (int)K, (int)card, total_range_bits, codes, c_s, c_k, c_t, (int64_t)0, dev_step,
+                       prev, err, slots, (int)n_max);
     ENCX_CHECK_LAUNCH();
     return 0;
 }

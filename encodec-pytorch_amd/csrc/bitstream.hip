@@ -7,6 +7,9 @@
 // BitUnpacker.pull (binary.py:105-123) is the inverse. Both are pure byte/integer work and
 // HBM-bound: no LDS, no MFMA.
 // Several frames of equal (K, T) are handled by one launch at a fixed byte stride per frame.
+// The slots of a streaming step deliver unequal frame counts: encx_bitpack_slots /
+// encx_bitunpack_slots handle them in one launch too, each slot's count read from the device
+// slot table, one packet (header byte + payload) per slot (encx.h: the packet format).
 #include "common.h"
 
 namespace {
@@ -79,9 +82,120 @@ __global__ void bitunpack_kernel(const uint8_t* __restrict__ in, int64_t in_stri
     }
 }
 
+// ---- one packet per slot of a streaming step (encx.h: the slot table and the packet format)
+// The frames a slot delivers, from the slot table: clamped to 0..n_max, so whatever the table
+// holds no column past the call's n_max (and none past the slot's own count) is addressed.
+ENCX_DEV int slot_frames(const int32_t* slots, int b, int n_max) {
+    const int f = slots[2 * b];
+    return f < 0 ? 0 : (f > n_max ? n_max : f);
+}
+
+// bitpack_kernel's lane layout per slot, the slot's own n = frames * K values: lane g of slot b
+// owns codes 8g..8g+7 of the slot's t-major sequence and the payload bytes [g*bits, (g+1)*bits)
+// behind the header byte. Lanes past the slot's count leave without forming an address, so the
+// unread tail of a row (columns >= frames) may hold anything. Lane 0 writes the header and the
+// packet length (0 for a slot that sits out: no header either).
+__global__ void bitpack_slots_kernel(const int64_t* __restrict__ codes, int64_t s_b, int64_t s_k, int64_t s_t, int B,
+                                     int K, int n_max, int bits, const int32_t* __restrict__ slots,
+                                     uint8_t* __restrict__ out, int64_t out_stride, int64_t* __restrict__ nbytes,
+                                     int groups, int* __restrict__ err) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= B * groups) return;
+    const int b = j / groups, g = j - b * groups;
+    const int frames = slot_frames(slots, b, n_max);
+    const int n = frames * K;
+    if (g == 0) {
+        nbytes[b] = frames ? 1 + ((int64_t)n * bits + 7) / 8 : 0;
+        if (frames) out[b * out_stride] = (uint8_t)frames;
+    }
+    const int v0 = g * 8;
+    if (v0 >= n) return;
+    const int cnt = n - v0 < 8 ? n - v0 : 8;
+    int t = v0 / K, k = v0 - t * K;
+    const int64_t* src = codes + b * s_b;
+    uint8_t* dst = out + b * out_stride + 1 + (int64_t)g * bits;
+    uint64_t acc = 0, bad = 0;
+    int nb = 0;
+    for (int i = 0; i < cnt; ++i) {
+        const uint64_t val = (uint64_t)src[k * s_k + t * s_t];
+        bad |= val >> bits;
+        acc |= val << nb;
+        nb += bits;
+        while (nb >= 8) {
+            *dst++ = (uint8_t)(acc & 0xff);
+            acc >>= 8;
+            nb -= 8;
+        }
+        if (++k == K) { k = 0; ++t; }
+    }
+    if (nb) *dst = (uint8_t)(acc & 0xff);
+    if (bad) atomicOr(err, 1);
+}
+
+// The inverse over all n_max * K code positions of every slot: lane g reads its bytes of the
+// payload only where the slot delivers the code, and writes 0 past the slot's count.
+__global__ void bitunpack_slots_kernel(const uint8_t* __restrict__ in, int64_t in_stride, int B, int K, int n_max,
+                                       int bits, const int32_t* __restrict__ slots, int64_t* __restrict__ codes,
+                                       int64_t s_b, int64_t s_k, int64_t s_t, int groups) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= B * groups) return;
+    const int b = j / groups, g = j - b * groups;
+    const int n = slot_frames(slots, b, n_max) * K, total = n_max * K;
+    const int v0 = g * 8;
+    const int cnt = total - v0 < 8 ? total - v0 : 8;
+    int t = v0 / K, k = v0 - t * K;
+    const uint8_t* src = in + b * in_stride + (int64_t)g * bits;
+    int64_t* dst = codes + b * s_b;
+    const uint64_t mask = (1ull << bits) - 1;
+    uint64_t acc = 0;
+    int nb = 0;
+    for (int i = 0; i < cnt; ++i) {
+        int64_t val = 0;
+        if (v0 + i < n) {
+            while (nb < bits) {
+                acc |= (uint64_t)(*src++) << nb;
+                nb += 8;
+            }
+            val = (int64_t)(acc & mask);
+            acc >>= bits;
+            nb -= bits;
+        }
+        dst[k * s_k + t * s_t] = val;
+        if (++k == K) { k = 0; ++t; }
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int encx_bitpack_slots(const int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t, int64_t B, int64_t K,
+                       int64_t n_max, int bits, const int32_t* slots, uint8_t* out, int64_t out_stride,
+                       int64_t* nbytes, int* err, encx_stream_t stream) {
+    ENCX_REQUIRE(codes && slots && out && nbytes && err);
+    ENCX_REQUIRE(B >= 1 && B <= 64 && K >= 1 && K <= 64 && n_max >= 1 && n_max <= 255 && bits >= 1 && bits <= 32);
+    ENCX_REQUIRE(out_stride >= 1 + encx_bitpack_bytes(n_max * K, bits));
+    const int groups = (int)cdiv(n_max * K, 8);
+    hipLaunchKernelGGL(bitpack_slots_kernel, dim3((unsigned)cdiv(B * groups, 256)), dim3(256), 0,
+                       (hipStream_t)stream, codes, s_b, s_k, s_t, (int)B, (int)K, (int)n_max, bits, slots, out,
+                       out_stride, nbytes, groups, err);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
+
+int encx_bitunpack_slots(const uint8_t* in, int64_t in_stride, int64_t B, int64_t K, int64_t n_max, int bits,
+                         const int32_t* slots, int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t,
+                         encx_stream_t stream) {
+    ENCX_REQUIRE(in && slots && codes);
+    ENCX_REQUIRE(B >= 1 && B <= 64 && K >= 1 && K <= 64 && n_max >= 1 && n_max <= 255 && bits >= 1 && bits <= 32);
+    ENCX_REQUIRE(in_stride >= encx_bitpack_bytes(n_max * K, bits));
+    const int groups = (int)cdiv(n_max * K, 8);
+    hipLaunchKernelGGL(bitunpack_slots_kernel, dim3((unsigned)cdiv(B * groups, 256)), dim3(256), 0,
+                       (hipStream_t)stream, in, in_stride, (int)B, (int)K, (int)n_max, bits, slots, codes, s_b, s_k,
+                       s_t, groups);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
 
 int64_t encx_bitpack_bytes(int64_t n_values, int bits) {
     if (n_values < 0 || bits < 1 || bits > 32) return -1;

@@ -17,6 +17,12 @@
 // zero vector each layer's state starts as (transformer.py:106): a real key, with k = the
 // in_proj bias and v = its bias, which the attention reads from the bias (never stored). Query s attends positions [max(0, s - P), s], P = past_context:
 // exactly the keys the reference's truncated state + mask leave (transformer.py:52-58, 117-118).
+//
+// Live streams (encx_lm_input_slots, encx_lm_layer_slots, encx_lm_slots_advance): each slot of
+// a streaming session has its own position pos[b] and next input prev[b][K] in device memory,
+// and the cache is a ring of R >= P + n_max rows per slot indexed position mod R, so a stream has
+// no length limit. The rows' positions come from the slot table (SlotRows); the arithmetic of a
+// row is the text above, unchanged, so its bits equal the linear cache's at the same position.
 #include "common.h"
 #include "gemm.h"
 
@@ -54,6 +60,51 @@ struct EpQKV {
             const int b = (int)fdiv((uint32_t)m, fT), t = m - b * T;
             const int64_t s = seq0 + (dstep ? *dstep : 0) + t;
             kv[((int64_t)b * L + s) * (2 * D) + (n - D)] = r;
+        }
+    }
+};
+
+// ---- per-slot streams (encx.h: encx_lm_input_slots and what follows it)
+// Row t of slot b is step tt = t + *dstep of the slot's chunk, at sequence position
+// pos[b] + 1 + tt; a slot on its first chunk takes pos as 0. live: the slot delivers that step
+// (tt < its count, clamped to n_max); only live rows write the ring or read the codes.
+struct SlotRows {
+    const int32_t* slots;
+    const int64_t* pos;
+    const int64_t* dstep;  // nullable
+    int n_max;
+    int64_t R;             // ring rows per slot
+    ENCX_DEV void at(int b, int t, int& tt, bool& live, bool& first, int64_t& s) const {
+        tt = t + (dstep ? (int)*dstep : 0);
+        int frames = slots[2 * b];
+        frames = frames < 0 ? 0 : (frames > n_max ? n_max : frames);
+        first = slots[2 * b + 1] != 0;
+        live = tt >= 0 && tt < frames;
+        const int64_t p = first ? 0 : pos[b];
+        s = (p < 0 ? 0 : p) + 1 + (tt < 0 ? 0 : (tt > n_max ? n_max : tt));
+    }
+};
+
+// in_proj of a slots step: as EpQKV, the (k | v) row into the slot's ring at position mod R,
+// and only for a live row
+struct EpQKVSlots {
+    const float* bias;
+    float* q;
+    float* kv;
+    int D, T;
+    SlotRows sr;
+    FastDiv fT;
+    ENCX_DEV void operator()(int m, int n, float v) const {
+        const float r = v + bias[n];
+        if (n < D) {
+            q[(int64_t)m * D + n] = r;
+        } else {
+            const int b = (int)fdiv((uint32_t)m, fT), t = m - b * T;
+            int tt;
+            bool live, first;
+            int64_t s;
+            sr.at(b, t, tt, live, first, s);
+            if (live) kv[((int64_t)b * sr.R + s % sr.R) * (2 * D) + (n - D)] = r;
         }
     }
 };
@@ -98,6 +149,11 @@ ENCX_DEV void ln_row(float (&v)[LN_MAXV], int D, const float* w, const float* b,
     }
 }
 
+// the row itself, from lane k's index `my` of codebook k and the row's step `pos` (below)
+ENCX_DEV void lm_input_row(int64_t my, int lane, int K, const float* __restrict__ emb, int64_t card1, int D,
+                           const float* ln_w, const float* ln_b, float pos, float max_period,
+                           float* __restrict__ out);
+
 // model.py:59-60 + transformer.py:108-113: x = LayerNorm(sum_k emb_k[idx]) + sin embedding.
 // One wave per row (b, t). shifted: idx(b,k,t) = t + offset == 0 ? 0 : codes[b][k][t-1] + 1
 // (the encoder's teacher-forced inputs, compress.py:74-79), else idx = codes[b][k][t].
@@ -118,6 +174,56 @@ __global__ __launch_bounds__(64) void lm_input_kernel(const int64_t* __restrict_
         if (shifted) my = (t == 0) ? 0 : idx[b * s_b + lane * s_k + (int64_t)(t - 1) * s_t] + 1;
         else my = idx[b * s_b + lane * s_k + (int64_t)t * s_t];
     }
+    lm_input_row(my, lane, K, emb, card1, D, ln_w, ln_b, (float)(offset + t), max_period, x + (int64_t)row * D);
+}
+
+// The same row for a slots step (SlotRows): the input of a live row is prev[b] (0 on a first
+// chunk) at step 0 of the chunk, or whenever there are no codes (the decoder, which carries
+// prev itself), and codes[b][k][tt - 1] + 1 after that. A dead row takes index 0, and every
+// index is clamped into the table: nothing in a slot's unread tail becomes an address.
+__global__ __launch_bounds__(64) void lm_input_slots_kernel(const int64_t* __restrict__ codes, int64_t s_b,
+                                                            int64_t s_k, int64_t s_t, int K, int T, SlotRows sr,
+                                                            const int64_t* __restrict__ prev,
+                                                            const float* __restrict__ emb, int64_t card1, int D,
+                                                            const float* ln_w, const float* ln_b, float max_period,
+                                                            float* __restrict__ x) {
+    const int row = blockIdx.x, lane = threadIdx.x;
+    const int b = row / T, t = row - b * T;
+    int tt;
+    bool live, first;
+    int64_t s;
+    sr.at(b, t, tt, live, first, s);
+    int64_t my = 0;
+    if (lane < K && live) {
+        if (codes && tt > 0) my = codes[b * s_b + lane * s_k + (int64_t)(tt - 1) * s_t] + 1;
+        else my = (first && tt == 0) ? 0 : prev[(int64_t)b * K + lane];
+        my = my < 0 ? 0 : (my >= card1 ? card1 - 1 : my);
+    }
+    lm_input_row(my, lane, K, emb, card1, D, ln_w, ln_b, (float)(s - 1), max_period, x + (int64_t)row * D);
+}
+
+// pos[b] += the slot's count (from 0 on a first chunk); with codes, prev[b][k] = 1 + the last
+// code the slot delivered (the encoder; the decoder's prev is written by encx_ac_decode_slots)
+__global__ void lm_slots_advance_kernel(const int32_t* __restrict__ slots, int B, int K, int n_max,
+                                        int64_t* __restrict__ pos, int64_t* __restrict__ prev,
+                                        const int64_t* __restrict__ codes, int64_t s_b, int64_t s_k, int64_t s_t,
+                                        int64_t card1) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * K) return;
+    const int b = i / K, k = i - b * K;
+    int frames = slots[2 * b];
+    frames = frames < 0 ? 0 : (frames > n_max ? n_max : frames);
+    if (!frames) return;
+    if (codes) {
+        int64_t c = codes[b * s_b + k * s_k + (int64_t)(frames - 1) * s_t] + 1;
+        prev[i] = c < 0 ? 0 : (c >= card1 ? card1 - 1 : c);
+    }
+    if (k == 0) pos[b] = (slots[2 * b + 1] ? 0 : pos[b]) + frames;
+}
+
+ENCX_DEV void lm_input_row(int64_t my, int lane, int K, const float* __restrict__ emb, int64_t card1, int D,
+                           const float* ln_w, const float* ln_b, float pos, float max_period,
+                           float* __restrict__ out) {
     float v[LN_MAXV];
 #pragma unroll
     for (int i = 0; i < LN_MAXV; ++i) v[i] = 0.f;
@@ -141,8 +247,6 @@ __global__ __launch_bounds__(64) void lm_input_kernel(const int64_t* __restrict_
     ln_row(v, D, ln_w, ln_b, lane);
     // create_sin_embedding (transformer.py:16-27): phase = pos / max_period^(i / (half - 1))
     const int half = D / 2;
-    const float pos = (float)(offset + t);
-    float* out = x + (int64_t)row * D;
 #pragma unroll
     for (int i = 0; i < LN_MAXV; ++i) {
         const int d = lane + 64 * i;
@@ -186,14 +290,21 @@ ENCX_DEV float sel(bool c, float v) { return c ? v : 0.f; }
 ENCX_DEV const float* kv_row(const float* kv, const float* in_b, int64_t base, int64_t pos, int D, int hoff, int v) {
     return pos == 0 ? in_b + D + v * D + hoff : kv + (base + pos) * (2 * D) + v * D + hoff;
 }
+// the same on a ring of L rows per stream (a slots step): absolute position pos lives in row pos mod L
+ENCX_DEV const float* kv_ring(const float* kv, const float* in_b, int64_t base, int64_t pos, int64_t L, int D, int hoff,
+                              int v) {
+    return pos == 0 ? in_b + D + v * D + hoff : kv + (base + pos % L) * (2 * D) + v * D + hoff;
+}
 
 // a few rows: one 256-thread workgroup per (row, head); dynamic LDS = scores / weights [P + 1]
 // + the window's values [P + 1][hd]
-template <int HD>
+// SLOTS (encx_lm_layer_slots): the row's position comes from the slot table (SlotRows) and the
+// cache is a ring; a dead row leaves with a zero context. The arithmetic is the same text.
+template <int HD, bool SLOTS>
 __global__ __launch_bounds__(256) void lm_attn_row_kernel(const float* __restrict__ q, const float* __restrict__ kv,
                                                           const float* __restrict__ in_b, float* __restrict__ ctx,
                                                           int T, int D, int H, int64_t L, int64_t seq0,
-                                                          const int64_t* dstep, int64_t P) {
+                                                          const int64_t* dstep, int64_t P, SlotRows sr) {
     extern __shared__ float sh[];
     __shared__ float red[8];
     __shared__ float Ssh;
@@ -201,7 +312,16 @@ __global__ __launch_bounds__(256) void lm_attn_row_kernel(const float* __restric
     const int row = blockIdx.x / H, h = blockIdx.x - row * H;
     const int b = row / T, t = row - b * T;
     const int hd = D / H, hoff = h * hd;
-    const int64_t s = seq0 + (dstep ? *dstep : 0) + t;
+    int64_t s = seq0 + (!SLOTS && dstep ? *dstep : 0) + t;
+    if (SLOTS) {
+        int tt;
+        bool live, first;
+        sr.at(b, t, tt, live, first, s);
+        if (!live) {  // block-uniform
+            if (tid < hd) ctx[(int64_t)row * D + hoff + tid] = 0.f;
+            return;
+        }
+    }
     const int64_t s0 = s - P > 0 ? s - P : 0;
     const int nk = (int)(s - s0 + 1);
     const int64_t base = (int64_t)b * L;
@@ -215,11 +335,12 @@ __global__ __launch_bounds__(256) void lm_attn_row_kernel(const float* __restric
     // values of the window into LDS (coalesced along d), scores of this thread's keys
     for (int i = tid; i < nk * hd; i += 256) {
         const int j = i / hd, d = i - j * hd;
-        vs[i] = kv_row(kv, in_b, base, s0 + j, D, hoff, 1)[d];
+        vs[i] = (SLOTS ? kv_ring(kv, in_b, base, s0 + j, L, D, hoff, 1) : kv_row(kv, in_b, base, s0 + j, D, hoff, 1))[d];
     }
     float mx = -INFINITY;
     for (int j = tid; j < nk; j += 256) {
-        const float* kr = kv_row(kv, in_b, base, s0 + j, D, hoff, 0);
+        const float* kr = SLOTS ? kv_ring(kv, in_b, base, s0 + j, L, D, hoff, 0)
+                                : kv_row(kv, in_b, base, s0 + j, D, hoff, 0);
         float kk[HD];
 #pragma unroll
         for (int d = 0; d < HD; ++d) kk[d] = kr[dcl(d, hd)];
@@ -444,14 +565,21 @@ int encx_lm_input(const int64_t* idx, int64_t s_b, int64_t s_k, int64_t s_t, int
     return 0;
 }
 
-int encx_lm_layer(const float* x, float* y, int64_t B, int64_t T, float* kv, int64_t L, int64_t seq0,
-                  const int64_t* dev_step, int64_t past_context, int64_t D, int64_t heads, int64_t F, const float* in_w,
-                  const float* in_b, const float* out_w, const float* out_b, const float* l1_w,
-                  const float* l1_b, const float* l2_w, const float* l2_b, const float* n1_w,
-                  const float* n1_b, const float* n2_w, const float* n2_b, float* work,
-                  encx_stream_t stream) {
+}  // extern "C"
+
+namespace {
+
+// the layer behind encx_lm_layer (sr == NULL: a linear cache of L rows from seq0) and
+// encx_lm_layer_slots (the positions from the slot table, a ring of L rows)
+int lm_layer_run(const float* x, float* y, int64_t B, int64_t T, float* kv, int64_t L, int64_t seq0,
+                 const int64_t* dev_step, int64_t past_context, int64_t D, int64_t heads, int64_t F, const float* in_w,
+                 const float* in_b, const float* out_w, const float* out_b, const float* l1_w,
+                 const float* l1_b, const float* l2_w, const float* l2_b, const float* n1_w,
+                 const float* n1_b, const float* n2_w, const float* n2_b, float* work, const SlotRows* sr,
+                 encx_stream_t stream) {
     ENCX_REQUIRE(B >= 1 && T >= 0 && D >= 1 && heads >= 1 && D % heads == 0 && D <= 64 * LN_MAXV);
-    ENCX_REQUIRE(D / heads <= 64 && F >= 1 && past_context >= 0 && seq0 >= 1 && seq0 + T <= L);
+    ENCX_REQUIRE(D / heads <= 64 && F >= 1 && past_context >= 0);
+    ENCX_REQUIRE(sr ? L >= past_context + T : (seq0 >= 1 && seq0 + T <= L));
     const int64_t N = B * T;
     if (N == 0) return 0;
     ENCX_REQUIRE(x && y && kv && in_w && in_b && out_w && out_b && l1_w && l1_b && l2_w && l2_b);
@@ -465,23 +593,44 @@ int encx_lm_layer(const float* x, float* y, int64_t B, int64_t T, float* kv, int
     float* ff = x1 + N * D;
     float* h2 = ff + N * F;
     // in_proj (MultiheadAttention), q to the work buffer, k | v into the cache
-    int rc = lm_linear(x, d, in_w, d, n, 3 * d, d,
-                       EpQKV{in_b, q, kv, d, (int)T, L, seq0, dev_step, make_fastdiv((uint32_t)T)}, st);
+    int rc = sr ? lm_linear(x, d, in_w, d, n, 3 * d, d,
+                            EpQKVSlots{in_b, q, kv, d, (int)T, *sr, make_fastdiv((uint32_t)T)}, st)
+                : lm_linear(x, d, in_w, d, n, 3 * d, d,
+                            EpQKV{in_b, q, kv, d, (int)T, L, seq0, dev_step, make_fastdiv((uint32_t)T)}, st);
     if (rc) return rc;
     const int64_t P = past_context;
     // with a device-side step the window is unknown here: size for the full P + 1
-    const int64_t win = (P + 1 < seq0 + T || dev_step) ? P + 1 : seq0 + T;
+    const int64_t win = (P + 1 < seq0 + T || dev_step || sr) ? P + 1 : seq0 + T;
     const int hd = (int)(D / heads);
     ENCX_REQUIRE(N * heads <= INT32_MAX);
-    if (N * heads <= 4096 || dev_step) {
+    if (sr) {  // a step has at most 64 slots x 255 frames; the row kernel serves them all
+        const size_t lds = (size_t)win * (hd + 1) * sizeof(float);
+        ENCX_REQUIRE(lds <= 150 * 1024);
+        // a past_context near 1000 needs more than the default dynamic LDS limit: raised once per
+        // size (by the eager step that precedes any capture), not on every launch
+        static size_t raised[2] = {64 * 1024, 64 * 1024};
+        if (lds > raised[hd > 32]) {
+            const void* fn = hd <= 32 ? (const void*)lm_attn_row_kernel<32, true>
+                                      : (const void*)lm_attn_row_kernel<64, true>;
+            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return (int)e;
+            raised[hd > 32] = lds;
+        }
+        if (hd <= 32)
+            hipLaunchKernelGGL((lm_attn_row_kernel<32, true>), dim3((unsigned)(N * heads)), dim3(256), lds, st, q, kv,
+                               in_b, ctx, (int)T, d, (int)heads, L, seq0, dev_step, P, *sr);
+        else
+            hipLaunchKernelGGL((lm_attn_row_kernel<64, true>), dim3((unsigned)(N * heads)), dim3(256), lds, st, q, kv,
+                               in_b, ctx, (int)T, d, (int)heads, L, seq0, dev_step, P, *sr);
+    } else if (N * heads <= 4096 || dev_step) {
         const size_t lds = (size_t)win * (hd + 1) * sizeof(float);
         ENCX_REQUIRE(lds <= 150 * 1024);
         if (hd <= 32)
-            hipLaunchKernelGGL(lm_attn_row_kernel<32>, dim3((unsigned)(N * heads)), dim3(256), lds, st, q, kv, in_b,
-                               ctx, (int)T, d, (int)heads, L, seq0, dev_step, P);
+            hipLaunchKernelGGL((lm_attn_row_kernel<32, false>), dim3((unsigned)(N * heads)), dim3(256), lds, st, q, kv,
+                               in_b, ctx, (int)T, d, (int)heads, L, seq0, dev_step, P, SlotRows{});
         else
-            hipLaunchKernelGGL(lm_attn_row_kernel<64>, dim3((unsigned)(N * heads)), dim3(256), lds, st, q, kv, in_b,
-                               ctx, (int)T, d, (int)heads, L, seq0, dev_step, P);
+            hipLaunchKernelGGL((lm_attn_row_kernel<64, false>), dim3((unsigned)(N * heads)), dim3(256), lds, st, q, kv,
+                               in_b, ctx, (int)T, d, (int)heads, L, seq0, dev_step, P, SlotRows{});
     } else {
         const int tblocks = (int)cdiv(T, 64);
         const int64_t nw = B * heads * tblocks;
@@ -505,6 +654,59 @@ int encx_lm_layer(const float* x, float* y, int64_t B, int64_t T, float* kv, int
     rc = lm_linear(ff, f, l2_w, f, n, d, f, EpBias<false>{l2_b, x1, h2, d}, st);
     if (rc) return rc;
     hipLaunchKernelGGL(lm_ln_kernel, dim3((unsigned)N), dim3(64), 0, st, h2, d, n2_w, n2_b, y);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int encx_lm_layer(const float* x, float* y, int64_t B, int64_t T, float* kv, int64_t L, int64_t seq0,
+                  const int64_t* dev_step, int64_t past_context, int64_t D, int64_t heads, int64_t F, const float* in_w,
+                  const float* in_b, const float* out_w, const float* out_b, const float* l1_w,
+                  const float* l1_b, const float* l2_w, const float* l2_b, const float* n1_w,
+                  const float* n1_b, const float* n2_w, const float* n2_b, float* work,
+                  encx_stream_t stream) {
+    return lm_layer_run(x, y, B, T, kv, L, seq0, dev_step, past_context, D, heads, F, in_w, in_b, out_w, out_b, l1_w,
+                        l1_b, l2_w, l2_b, n1_w, n1_b, n2_w, n2_b, work, nullptr, stream);
+}
+
+int encx_lm_input_slots(const int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t, int64_t B, int64_t K,
+                        int64_t T, int64_t n_max, const int32_t* slots, const int64_t* pos, const int64_t* prev,
+                        const int64_t* dev_step, const float* emb, int64_t card1, int64_t D, const float* ln_w,
+                        const float* ln_b, float max_period, float* x, encx_stream_t stream) {
+    ENCX_REQUIRE(slots && pos && prev && emb && ln_w && ln_b && x);
+    ENCX_REQUIRE(B >= 1 && B <= 64 && K >= 1 && K <= 64 && n_max >= 1 && n_max <= 255 && T >= 1 && T <= n_max);
+    ENCX_REQUIRE(D >= 4 && D % 2 == 0 && D <= 64 * LN_MAXV && card1 >= 1);
+    hipLaunchKernelGGL(lm_input_slots_kernel, dim3((unsigned)(B * T)), dim3(64), 0, (hipStream_t)stream, codes, s_b,
+                       s_k, s_t, (int)K, (int)T, SlotRows{slots, pos, dev_step, (int)n_max, 0}, prev, emb, card1,
+                       (int)D, ln_w, ln_b, max_period, x);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
+
+int encx_lm_layer_slots(const float* x, float* y, int64_t B, int64_t T, int64_t n_max, float* kv, int64_t R,
+                        const int32_t* slots, const int64_t* pos, const int64_t* dev_step, int64_t past_context,
+                        int64_t D, int64_t heads, int64_t F, const float* in_w, const float* in_b, const float* out_w,
+                        const float* out_b, const float* l1_w, const float* l1_b, const float* l2_w,
+                        const float* l2_b, const float* n1_w, const float* n1_b, const float* n2_w,
+                        const float* n2_b, float* work, encx_stream_t stream) {
+    ENCX_REQUIRE(slots && pos && x && y && kv && work);
+    ENCX_REQUIRE(B >= 1 && B <= 64 && n_max >= 1 && n_max <= 255 && T >= 1 && T <= n_max);
+    ENCX_REQUIRE(past_context >= 0 && R >= past_context + n_max);
+    const SlotRows sr{slots, pos, dev_step, (int)n_max, R};
+    return lm_layer_run(x, y, B, T, kv, R, 1, nullptr, past_context, D, heads, F, in_w, in_b, out_w, out_b, l1_w, l1_b,
+                        l2_w, l2_b, n1_w, n1_b, n2_w, n2_b, work, &sr, stream);
+}
+
+int encx_lm_slots_advance(const int32_t* slots, int64_t B, int64_t K, int64_t n_max, int64_t* pos, int64_t* prev,
+                          const int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t, int64_t card1,
+                          encx_stream_t stream) {
+    ENCX_REQUIRE(slots && pos && prev);
+    ENCX_REQUIRE(B >= 1 && B <= 64 && K >= 1 && K <= 64 && n_max >= 1 && n_max <= 255 && card1 >= 1);
+    hipLaunchKernelGGL(lm_slots_advance_kernel, dim3((unsigned)cdiv(B * K, 256)), dim3(256), 0, (hipStream_t)stream,
+                       slots, (int)B, (int)K, (int)n_max, pos, prev, codes, s_b, s_k, s_t, card1);
     ENCX_CHECK_LAUNCH();
     return 0;
 }

@@ -14,6 +14,11 @@ is known), the decoder one step per launch sequence; csrc/lm.hip computes every 
 fixed order that does not depend on the rows sharing the launch, so both sides produce the
 same cdfs bit for bit.
 
+`LMStreamEncoder` / `LMStreamDecoder` are the same coder for live streams (the slots of
+encx/streaming.py): one flushed coder run per slot and step, the LM's position, last codes and
+key/value ring carried per slot on the device, so a stream has no length limit and a captured
+step replays whatever the slots deliver.
+
 `nll(codes)` trains the LM (csrc/lm_train.hip): the teacher-forced forward is the encoder's own
 pass, so the loss is the log-probability the arithmetic coder will see, and one autograd Function
 runs the hand-written backward and hands every parameter its gradient.
@@ -472,3 +477,287 @@ class LMModel(nn.Module):
         if any(e):
             raise RuntimeError(f'encx arithmetic decoder failed: {e}')
         return codes, [(p + 7) // 8 for p in dstate[:, ENCX_AC_POS].cpu().tolist()]
+
+
+# ---------------------------------------------------------------------------- live streams
+MAX_SLOTS = 64          # encx.h: the slot table's B
+MAX_PACKET_FRAMES = 255  # the packet's header byte
+
+
+class _LMSlots:
+    """What LMStreamEncoder and LMStreamDecoder share: the per-slot LM state on the device
+    (pos [B], prev [B][K], one key/value ring [B][R][2 dim] per layer, R = past_context +
+    max_frames), the slot table the kernels read (encx.h) and the host's view of each slot.
+    Nothing touches the device before the first valid step, so every refusal of a step's
+    arguments is a pure host check. A session is a snapshot of the LM's stacked heads and
+    embeddings: build a new one after changing the LM's weights."""
+
+    def __init__(self, lm: 'LMModel', batch: int, K: int, max_frames: int, graphs: bool):
+        if not 1 <= batch <= MAX_SLOTS:
+            raise ValueError(f'encx LM streaming: batch {batch} (1..{MAX_SLOTS})')
+        if not 1 <= K <= min(lm.n_q, 64):
+            raise ValueError(f'encx LM streaming: {K} codebooks for an LM of n_q={lm.n_q} (at most 64)')
+        if not 1 <= max_frames <= MAX_PACKET_FRAMES:
+            raise ValueError(f'encx LM streaming: max_frames {max_frames} (1..{MAX_PACKET_FRAMES})')
+        self.lm, self.B, self.K = lm, int(batch), int(K)
+        self.max_frames, self.graphs = int(max_frames), bool(graphs)
+        self.R = int(lm.transformer.past_context) + self.max_frames
+        self.started = [False] * self.B
+        self.failed: tp.Set[int] = set()
+        self._ready = False
+        self._tab = None  # the slot table as last uploaded
+        self._graphs: tp.Dict[int, tp.Any] = {}
+
+    def reset(self):
+        """Every slot starts a new stream with its next packet."""
+        self.started = [False] * self.B
+        self.failed.clear()
+
+    def restart(self, slots):
+        """The named slots start a new stream with their next packet: the LM's position and
+        context are taken as empty by the kernels on that packet (the slot table's first-chunk
+        flag), so this launches nothing and disturbs no other slot."""
+        from .streaming import check_restart
+        for b in check_restart(slots, self.B):
+            self.started[b] = False
+            self.failed.discard(b)
+
+    def _check_frames(self, frames):
+        from .streaming import check_frames, _ints
+        frames = _ints(frames, 'frames')
+        n_max, _ = check_frames(self.started, frames, 1, self.max_frames)
+        for b, f in enumerate(frames):
+            if f and b in self.failed:
+                raise ValueError(f'encx LM streaming: slot {b} failed on a bad packet; restart([{b}]) it first')
+        return frames, n_max
+
+    def _ensure(self):
+        if self._ready:
+            return
+        lm = self.lm
+        self._packed = lm._packed()  # kept: the captured graphs point at these stacks
+        lm._check_device()
+        dev = self.dev = lm._emb.device
+        tr = lm.transformer
+        B, K = self.B, self.K
+        self._kv = [torch.zeros(B, self.R, 2 * lm.dim, device=dev) for _ in tr.layers]
+        self._pos = torch.zeros(B, dtype=torch.int64, device=dev)
+        self._prev = torch.zeros(B, K, dtype=torch.int64, device=dev)
+        self._slots = torch.zeros(B, 2, dtype=torch.int32, device=dev)
+        self._cols = torch.arange(self.max_frames, device=dev, dtype=torch.int32)
+        self._ready = True
+
+    def _put_slots(self, frames):
+        tab = [(int(f), int(f > 0 and not on)) for f, on in zip(frames, self.started)]
+        if tab != self._tab:  # a sustained step repeats its table: no upload
+            self._slots.copy_(torch.tensor(tab, dtype=torch.int32))
+            self._tab = tab
+
+    def _rows(self, T, n_max, codes, dstep):
+        """The LM input and every layer for T rows per slot under the slot table -> x [B*T][dim]."""
+        lm, tr = self.lm, self.lm.transformer
+        B, K, D, Fh = self.B, self.K, lm.dim, tr.hidden
+        st = stream()
+        cs = codes.stride() if codes is not None else (0, 0, 0)
+        dptr = dstep.data_ptr() if dstep is not None else None
+        x = torch.empty(B * T, D, device=self.dev)
+        call('encx_lm_input_slots', codes.data_ptr() if codes is not None else None, cs[0], cs[1], cs[2], B, K, T,
+             n_max, self._slots.data_ptr(), self._pos.data_ptr(), self._prev.data_ptr(), dptr, lm._emb.data_ptr(),
+             lm.card + 1, D, tr.norm_in.weight.data_ptr(), tr.norm_in.bias.data_ptr(), float(tr.max_period),
+             x.data_ptr(), st)
+        work = torch.empty((int(lib.encx_lm_layer_workspace(B * T, D, Fh)) + 3) // 4, device=self.dev)
+        for i, layer in enumerate(tr.layers):
+            y = torch.empty_like(x)
+            call('encx_lm_layer_slots', x.data_ptr(), y.data_ptr(), B, T, n_max, self._kv[i].data_ptr(), self.R,
+                 self._slots.data_ptr(), self._pos.data_ptr(), dptr, tr.past_context, D, tr.num_heads, Fh,
+                 *_layer_ptrs(layer), work.data_ptr(), st)
+            x = y
+        return x
+
+    def _advance(self, n_max, codes):
+        cs = codes.stride() if codes is not None else (0, 0, 0)
+        call('encx_lm_slots_advance', self._slots.data_ptr(), self.B, self.K, n_max, self._pos.data_ptr(),
+             self._prev.data_ptr(), codes.data_ptr() if codes is not None else None, cs[0], cs[1], cs[2],
+             self.lm.card + 1, stream())
+
+    def _run(self, key, body, frames):
+        """Fill this step's slot table; -> the graph of body(key) to replay, or None (run the body
+        eagerly). The first step of a key runs the body once eagerly under an EMPTY table (every
+        row dead: each kernel is loaded, no state moves), then captures it; the table is device
+        memory, so the graph replays for any counts."""
+        if not self.graphs:
+            self._put_slots(frames)
+            return None
+        g = self._graphs.get(key)
+        if g is None:
+            self._slots.zero_()
+            self._tab = None
+            body(key)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):  # one stream: no parallel branches
+                body(key)
+            self._graphs[key] = g
+        self._put_slots(frames)
+        return g
+
+
+class LMStreamEncoder(_LMSlots):
+    """Arithmetic-codes the chunks of `batch` live streams (the slots of a StreamEncoder) under
+    `lm`, one self-contained packet per delivering slot and step, the LM's context carried from
+    packet to packet for a stream of any length (the packet format: include/encx.h).
+
+        enc = LMStreamEncoder(lm, batch=64, K=8)
+        payloads = enc.encode_slots(codes, frames)   # codes [B, K, max(frames)] int64 on the GPU
+
+    payloads[b] is the coded chunk of slot b (b'' for a slot with 0 frames); packets(...) returns
+    the same with the header byte in front. Slot b's columns past frames[b] are not read. A slot's
+    bytes are those of the same stream alone in a session of one. probas=True keeps the
+    probabilities of the last step's rows in last_probas [B, n_max, K, card]."""
+
+    def __init__(self, lm, batch: int, K: int, max_frames: int = 8, graphs: bool = True, probas: bool = False):
+        super().__init__(lm, batch, K, max_frames, graphs)
+        self._want_probas = bool(probas)
+        self._bufs: tp.Dict[int, tp.Any] = {}
+        self.last_probas = self.last_cdf = None
+
+    def _buf(self, n):
+        b = self._bufs.get(n)
+        if b is None:
+            dev, B, K, card = self.dev, self.B, self.K, self.lm.card
+            stride = 1 + int(lib.encx_ac_encode_capacity(n * K, TOTAL_RANGE_BITS))
+            b = self._bufs[n] = dict(
+                codes=torch.zeros(B, K, n, dtype=torch.int64, device=dev),
+                lohi=torch.zeros(B, n, K, 2, dtype=torch.int32, device=dev),
+                cdf=torch.empty(B, n, K, card, dtype=torch.int32, device=dev),
+                probas=torch.empty(B, n, K, card, device=dev) if self._want_probas else None,
+                out=torch.zeros(B, stride, dtype=torch.uint8, device=dev),
+                nbytes=torch.zeros(B, dtype=torch.int64, device=dev),
+                serr=torch.zeros(B, dtype=torch.int32, device=dev),
+                err=torch.zeros(1, dtype=torch.int32, device=dev))
+        return b
+
+    def _body(self, n):
+        b = self._buf(n)
+        x = self._rows(n, n, b['codes'], None)
+        b['err'].zero_()
+        self.lm._heads(x, self.B, n, self.K, probas=b['probas'], cdf=b['cdf'], sym=b['codes'], lohi=b['lohi'],
+                       err=b['err'])
+        call('encx_ac_encode_slots', b['lohi'].data_ptr(), self.B, n, self.K, self._slots.data_ptr(),
+             TOTAL_RANGE_BITS, b['out'].data_ptr(), b['out'].shape[1], b['nbytes'].data_ptr(),
+             b['serr'].data_ptr(), stream())
+        self._advance(n, b['codes'])
+
+    @torch.no_grad()
+    def packets(self, codes: torch.Tensor, frames: tp.Sequence[int]) -> tp.List[bytes]:
+        """One packet (header byte + coded payload) per slot, b'' for a slot with 0 frames."""
+        frames, n_max = self._check_frames(frames)
+        if codes.dim() != 3 or tuple(codes.shape) != (self.B, self.K, n_max) or codes.dtype != torch.int64:
+            raise ValueError(f'encx LM streaming: expected int64 codes [{self.B}, {self.K}, max(frames) = {n_max}], '
+                             f'got {codes.dtype} {tuple(codes.shape)}')
+        if not codes.is_cuda:
+            raise RuntimeError('encx LM streaming takes device tensors (no CPU fallback)')
+        self._ensure()
+        b = self._buf(n_max)
+        g = self._run(n_max, self._body, frames)
+        # the graph's own input; past a slot's count whatever the caller left becomes code 0
+        keep = (self._cols[:n_max] < self._slots[:, :1]).unsqueeze(1)
+        b['codes'].copy_(torch.where(keep, codes, 0))
+        if g is not None:
+            g.replay()
+        else:
+            self._body(n_max)
+        self.last_probas, self.last_cdf = b['probas'], b['cdf']
+        host, nb = b['out'].cpu(), b['nbytes'].cpu().tolist()
+        e, e0 = b['serr'].cpu().tolist(), int(b['err'].item())
+        for s, f in enumerate(frames):
+            if f:
+                self.started[s] = True
+        if e0 & 2:
+            raise ValueError(f'a code is outside [0, {self.lm.card})')
+        if e0 & 1 or any(v == 1 for v in e):
+            raise AssertionError('quantized cdf total above 2^total_range_bits (ac.py:50, 116)')
+        if any(e):
+            raise RuntimeError(f'encx arithmetic coder failed: {e}')
+        return [host[s, :nb[s]].numpy().tobytes() for s in range(self.B)]
+
+    def encode_slots(self, codes: torch.Tensor, frames: tp.Sequence[int]) -> tp.List[bytes]:
+        """The coded payloads (the packets without their header byte)."""
+        return [p[1:] for p in self.packets(codes, frames)]
+
+
+class LMStreamDecoder(_LMSlots):
+    """The inverse of LMStreamEncoder: decode_slots(payloads, frames) -> (codes [B, K, max(frames)]
+    int64 on the GPU, zero past each slot's count, and the list of slots that failed in this
+    step). One step of the chunk = LM input, layers, heads + cdf, arithmetic decode of the K
+    codes, for one row per slot; it is captured once and replayed max(frames) times with the step
+    in a device counter. A packet the coder cannot decode (it runs dry, or no interval holds the
+    value) is data, not an error: that slot comes back with zero codes, is listed in `failed`, and
+    refuses further packets until restart([b]); the other slots are not disturbed."""
+
+    def __init__(self, lm, batch: int, K: int, max_frames: int = 8, graphs: bool = True):
+        super().__init__(lm, batch, K, max_frames, graphs)
+        self.cap = int(lib.encx_ac_encode_capacity(self.max_frames * self.K, TOTAL_RANGE_BITS))
+
+    def _ensure(self):
+        if self._ready:
+            return
+        super()._ensure()
+        dev, B, K, M = self.dev, self.B, self.K, self.max_frames
+        self._data = torch.zeros(B, self.cap, dtype=torch.uint8, device=dev)
+        self._nbytes = torch.zeros(B, dtype=torch.int64, device=dev)
+        self._dstate = new_decoder_state(B, dev)
+        self._err = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._codes = torch.zeros(B, K, M, dtype=torch.int64, device=dev)
+        self._cdf = torch.empty(B, 1, K, self.lm.card, dtype=torch.int32, device=dev)
+        self._step = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def _body(self, _key):
+        B, K, M = self.B, self.K, self.max_frames
+        x = self._rows(1, M, None, self._step)
+        self.lm._heads(x, B, 1, K, cdf=self._cdf)
+        st = stream()
+        call('encx_ac_decode_slots', self._data.data_ptr(), self.cap, self._nbytes.data_ptr(), B,
+             self._dstate.data_ptr(), self._cdf.data_ptr(), K, self.lm.card, TOTAL_RANGE_BITS,
+             self._codes.data_ptr(), K * M, M, 1, M, self._step.data_ptr(), self._slots.data_ptr(),
+             self._prev.data_ptr(), self._err.data_ptr(), st)
+        call('encx_lm_step_advance', self._step.data_ptr(), 1, st)
+
+    @torch.no_grad()
+    def decode_slots(self, payloads: tp.Sequence[bytes], frames: tp.Sequence[int]):
+        frames, n_max = self._check_frames(frames)
+        if len(payloads) != self.B:
+            raise ValueError(f'encx LM streaming: payloads for {len(payloads)} slots, the session has {self.B}')
+        for b, (p, f) in enumerate(zip(payloads, frames)):
+            if not isinstance(p, (bytes, bytearray)):
+                raise ValueError(f'encx LM streaming: the payload of slot {b} is not bytes')
+            if len(p) and not f:
+                raise ValueError(f'encx LM streaming: slot {b} has a payload but 0 frames')
+            if len(p) > self.cap:
+                raise ValueError(f'encx LM streaming: a payload of {len(p)} bytes in slot {b}; no packet of up to '
+                                 f'{self.max_frames} frames has more than {self.cap}')
+        self._ensure()
+        host = torch.zeros(self.B, self.cap, dtype=torch.uint8)
+        for b, p in enumerate(payloads):
+            if len(p):
+                host[b, :len(p)] = torch.frombuffer(bytearray(p), dtype=torch.uint8)
+        g = self._run(0, self._body, frames)
+        self._data.copy_(host)
+        self._nbytes.copy_(torch.tensor([len(p) for p in payloads], dtype=torch.int64))
+        self._codes.zero_()
+        self._err.zero_()
+        self._step.zero_()
+        for _ in range(n_max):
+            if g is not None:
+                g.replay()
+            else:
+                self._body(0)
+        self._advance(self.max_frames, None)
+        codes = self._codes[:, :, :n_max].clone()
+        failed = [b for b, v in enumerate(self._err.cpu().tolist()) if v]
+        for b, f in enumerate(frames):
+            if b in failed:
+                codes[b] = 0
+                self.failed.add(b)
+            elif f:
+                self.started[b] = True
+        return codes, failed

@@ -44,7 +44,20 @@ carried, and only the two places that carry state look at the per-slot counts (a
 device memory, read by the kernels): the window roll / first-chunk fill and the LSTM's h and c
 (csrc/stream.hip). encode(x) / decode(codes) are the uniform case. A slot's results are
 bit-identical to the same stream alone in a session of one. Not supported: a bandwidth (n_q) per
-slot, more than 64 slots, LM-coded streaming, an `.ecdc` container for live streams.
+slot, more than 64 slots, an `.ecdc` container for live streams.
+
+Packets. What goes on the wire is one self-contained packet per delivering slot and step
+(`StreamPacker` / `StreamUnpacker`; the format is documented in include/encx.h): a header byte
+with the frame count, then the codes bit-packed (one launch for all slots) or, with use_lm=True,
+arithmetic-coded under the entropy-coding LM. The coder is flushed at the end of every packet,
+so a packet decodes when it arrives; the LM's context is carried from packet to packet, per slot,
+on a ring cache, for a stream of any length (encx/lm.py LMStreamEncoder / LMStreamDecoder).
+
+    packer, unpacker = StreamPacker(model, 64, enc.n_q), StreamUnpacker(model, 64, enc.n_q)
+    packets = packer.pack_slots(codes, frames)        # list of bytes, b'' for a slot with 0 frames
+    codes, frames = unpacker.unpack_slots(packets)    # ready for dec.decode_slots(codes, frames)
+
+A lost packet is not concealed: restart([b]) on both sides is the remedy.
 
 Inference only. Weight-normed weights are prepared once, at construction; call
 refresh_weights() after changing the model. reset() restarts every slot.
@@ -739,3 +752,163 @@ class StreamDecoder:
         # clamped as in decode(); past a slot's count whatever the caller left becomes code 0
         buf.copy_(torch.where(s.keep(n, 1).squeeze(1), codes.permute(1, 0, 2).clamp(0, self.bins - 1), 0))
         return s._step_slots(frames, n_max, any_first, self._body_slots)[0]
+
+
+# ---------------------------------------------------------------------------- packets
+MAX_PACKET_FRAMES = 255  # the header byte (include/encx.h: the packet format)
+
+
+def packet_bytes(n: int, K: int, bits: int) -> int:
+    """Length of a raw packet of n frames of K codes: the header byte and ceil(n K bits / 8)."""
+    return 1 + (n * K * bits + 7) // 8
+
+
+class _Packets:
+    """What StreamPacker and StreamUnpacker share: the arguments, the LM session behind the
+    LM-coded form, and for the raw form a slot table and byte buffers on the device, made at the
+    first valid step (every refusal of a step's arguments is a pure host check)."""
+
+    def __init__(self, model, batch, n_q, use_lm, lm, max_frames, graphs, lm_session):
+        if not 1 <= batch <= MAX_BATCH:
+            raise ValueError(f'encx streaming: batch {batch} (1..{MAX_BATCH})')
+        if not 1 <= n_q <= min(model.quantizer.n_q, 64):
+            raise ValueError(f'encx streaming: n_q {n_q} (the model has {model.quantizer.n_q} codebooks; at most 64)')
+        if not 1 <= max_frames <= MAX_PACKET_FRAMES:
+            raise ValueError(f'encx streaming: max_frames {max_frames} (1..{MAX_PACKET_FRAMES})')
+        self.model, self.B, self.n_q = model, int(batch), int(n_q)
+        self.max_frames, self.use_lm = int(max_frames), bool(use_lm)
+        self.bits = int(model.bits_per_codebook)
+        self._lm = None
+        if self.use_lm:
+            self._lm = lm_session(lm if lm is not None else model.get_lm_model(), self.B, self.n_q,
+                                  self.max_frames, graphs)
+        self._dev = None
+
+    def reset(self):
+        """Every slot starts a new stream with its next packet (the raw form carries no state)."""
+        if self._lm is not None:
+            self._lm.reset()
+
+    def restart(self, slots):
+        """As StreamEncoder.restart: the named slots' next packet begins a stream."""
+        slots = check_restart(slots, self.B)
+        if self._lm is not None:
+            self._lm.restart(slots)
+
+    def _ensure(self):
+        if self._dev is None:
+            dev = next(self.model.parameters()).device
+            if dev.type != 'cuda':
+                raise RuntimeError('encx streaming runs on the GPU (no CPU fallback): move the model first')
+            ensure_device(dev)
+            self._stride = packet_bytes(self.max_frames, self.n_q, self.bits)
+            self._slots = torch.zeros(self.B, 2, dtype=torch.int32, device=dev)
+            self._bytes = torch.zeros(self.B, self._stride, dtype=torch.uint8, device=dev)
+            self._nbytes = torch.zeros(self.B, dtype=torch.int64, device=dev)
+            self._err = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._tab = None
+            self._dev = dev
+
+    def _put_slots(self, frames):
+        """The raw form's slot table (no first-chunk flag: it carries no state), uploaded only
+        when it differs from the last step's."""
+        tab = [(int(f), 0) for f in frames]
+        if tab != self._tab:
+            self._slots.copy_(torch.tensor(tab, dtype=torch.int32))
+            self._tab = tab
+
+
+class StreamPacker(_Packets):
+    """The codes of a slots step as one self-contained packet per delivering slot:
+
+        packer = StreamPacker(model, batch=64, n_q=enc.n_q)            # or use_lm=True
+        packets = packer.pack_slots(enc.encode_slots(x, frames), frames)   # list of bytes, b'' for 0 frames
+
+    Raw: header byte + the bit-packed codes, ONE launch for all slots whatever their counts.
+    use_lm=True: header byte + one arithmetic-coder run under `lm` (model.get_lm_model() when
+    None), the LM's context carried across a slot's packets (encx.lm.LMStreamEncoder). The
+    packet format is documented in include/encx.h. Slot b's codes past frames[b] are not read."""
+
+    def __init__(self, model, batch: int, n_q: int, use_lm: bool = False, lm=None, max_frames: int = 8,
+                 graphs: bool = True):
+        from .lm import LMStreamEncoder
+        super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamEncoder)
+
+    @torch.no_grad()
+    def pack_slots(self, codes: torch.Tensor, frames: tp.Sequence[int]) -> tp.List[bytes]:
+        if self._lm is not None:
+            return self._lm.packets(codes, frames)
+        frames = _ints(frames, 'frames')
+        n_max, _ = check_frames([True] * self.B, frames, 1, self.max_frames)
+        if codes.dim() != 3 or tuple(codes.shape) != (self.B, self.n_q, n_max) or codes.dtype != torch.int64:
+            raise ValueError(f'encx streaming: expected int64 codes [{self.B}, {self.n_q}, max(frames) = {n_max}], '
+                             f'got {codes.dtype} {tuple(codes.shape)}')
+        if not codes.is_cuda:
+            raise RuntimeError('encx streaming takes device tensors (no CPU fallback)')
+        self._ensure()
+        self._put_slots(frames)
+        self._err.zero_()
+        sb, sk, s_t = codes.stride()
+        call('encx_bitpack_slots', codes.data_ptr(), sb, sk, s_t, self.B, self.n_q, n_max, self.bits,
+             self._slots.data_ptr(), self._bytes.data_ptr(), self._stride, self._nbytes.data_ptr(),
+             self._err.data_ptr(), stream())
+        host = self._bytes.cpu()
+        if int(self._err.item()):
+            raise ValueError(f'encx streaming: a delivered code does not fit in {self.bits} bits')
+        return [host[b, :packet_bytes(f, self.n_q, self.bits)].numpy().tobytes() if f else b''
+                for b, f in enumerate(frames)]
+
+
+class StreamUnpacker(_Packets):
+    """The inverse of StreamPacker: unpack_slots(packets) -> (codes [B, n_q, max(frames)] int64 on
+    the GPU, zero past each slot's count, and frames), ready for StreamDecoder.decode_slots. A slot
+    with nothing to deliver passes b''. A bad LM packet is data: its slot comes back with 0 frames
+    and zero codes, is listed in `failed`, and refuses packets until restart([b])."""
+
+    def __init__(self, model, batch: int, n_q: int, use_lm: bool = False, lm=None, max_frames: int = 8,
+                 graphs: bool = True):
+        from .lm import LMStreamDecoder
+        super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamDecoder)
+
+    @property
+    def failed(self) -> tp.List[int]:
+        return sorted(self._lm.failed) if self._lm is not None else []
+
+    def _headers(self, packets):
+        if len(packets) != self.B:
+            raise ValueError(f'encx streaming: packets for {len(packets)} slots, the session has {self.B}')
+        frames = []
+        for b, p in enumerate(packets):
+            if not isinstance(p, (bytes, bytearray)):
+                raise ValueError(f'encx streaming: the packet of slot {b} is not bytes')
+            n = p[0] if len(p) else 0
+            if len(p) and not 1 <= n <= self.max_frames:
+                raise ValueError(f'encx streaming: the packet of slot {b} announces {n} frames '
+                                 f'(1..max_frames={self.max_frames})')
+            if len(p) and not self.use_lm and len(p) != packet_bytes(n, self.n_q, self.bits):
+                raise ValueError(f'encx streaming: a raw packet of {n} frames in slot {b} has '
+                                 f'{packet_bytes(n, self.n_q, self.bits)} bytes, not {len(p)}')
+            frames.append(int(n))
+        if not any(frames):
+            raise ValueError('encx streaming: no slot delivers a frame')
+        return frames
+
+    @torch.no_grad()
+    def unpack_slots(self, packets: tp.Sequence[bytes]):
+        frames = self._headers(packets)
+        if self._lm is not None:
+            codes, failed = self._lm.decode_slots([bytes(p[1:]) for p in packets], frames)
+            return codes, [0 if b in failed else f for b, f in enumerate(frames)]
+        n_max = max(frames)
+        self._ensure()
+        host = torch.zeros(self.B, self._stride, dtype=torch.uint8)
+        for b, p in enumerate(packets):
+            if len(p):
+                host[b, :len(p)] = torch.frombuffer(bytearray(p), dtype=torch.uint8)
+        self._bytes.copy_(host)
+        self._put_slots(frames)
+        codes = torch.empty(self.B, self.n_q, n_max, dtype=torch.int64, device=self._dev)
+        sb, sk, s_t = codes.stride()
+        call('encx_bitunpack_slots', self._bytes.data_ptr() + 1, self._stride, self.B, self.n_q, n_max, self.bits,
+             self._slots.data_ptr(), codes.data_ptr(), sb, sk, s_t, stream())
+        return codes, frames

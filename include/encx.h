@@ -826,6 +826,81 @@ int encx_stream_lstm_slots(const float* x, const float* wcatT, const float* bsum
                            int64_t x_rstride, int64_t out_bstride, int64_t out_rstride, const int32_t* slots,
                            encx_stream_t stream);
 
+/* ------------------------------------------------------ packets of a slots step (encx/streaming.py)
+ * PACKET FORMAT. One packet is one slot's chunk of one step: n latent frames, 1 <= n <= max_frames
+ * <= 255, of K codebooks. The transport carries the packet's length; there is no container.
+ *   byte 0     n
+ *   payload    the n*K codes, t-major then codebook (compress.py:88-98), in one of two forms:
+ *     raw  each code as `bits` bits of the little-endian BitPacker stream, the last partial byte
+ *          flushed: exactly encx_bitpack_bytes(n*K, bits) bytes, those of encx_bitpack for T = n.
+ *     LM   one ArithmeticCoder run (ac.py:130-167; total_range_bits 24, the cdfs of
+ *          build_stable_quantized_cdf as compress.py calls it), FLUSHED AT THE END OF THE PACKET:
+ *          a packet is decodable when it arrives. The coder starts anew in every packet; the LM
+ *          does not: the cdf row of the stream's frame t is the LM's row at stream position t given
+ *          every earlier code of that stream, whichever packets carried them.
+ * Every kernel below reads the slot table slots[2*B] described above (count, first-chunk flag),
+ * with the count clamped to 0..n_max, and never forms an address from a slot's unread tail
+ * (columns >= its count): dead rows may be computed, on indices replaced by 0. B and K are 1..64,
+ * n_max 1..255, bits 1..32; anything else, or a NULL pointer, is ENCX_EINVAL before any launch.
+ *
+ * encx_bitpack_slots: ONE launch for all slots. codes[b*s_b + k*s_k + t*s_t] int64; slot b's packet
+ * (header byte, raw payload) goes to out + b*out_stride (out_stride >= 1 + encx_bitpack_bytes(
+ * n_max*K, bits)) and its length to nbytes[b], 0 for a slot that delivers nothing (nothing is
+ * written for it). *err (device int, caller zeroed) gets 1 for a delivered code >= 2^bits.
+ * encx_bitunpack_slots: the inverse. Slot b's PAYLOAD is at in + b*in_stride (in_stride >=
+ * encx_bitpack_bytes(n_max*K, bits)); the host has put the counts of the header bytes into the
+ * table. Writes all n_max columns of codes, 0 past each slot's count. */
+int encx_bitpack_slots(const int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t, int64_t B, int64_t K,
+                       int64_t n_max, int bits, const int32_t* slots, uint8_t* out, int64_t out_stride,
+                       int64_t* nbytes, int* err, encx_stream_t stream);
+int encx_bitunpack_slots(const uint8_t* in, int64_t in_stride, int64_t B, int64_t K, int64_t n_max, int bits,
+                         const int32_t* slots, int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t,
+                         encx_stream_t stream);
+/* The LM over slots. Device state per slot: pos[b] (int64, frames coded so far) and prev[b][K]
+ * (int64, the LM input index of the slot's next row: 1 + its last code, 0 at the start of a
+ * stream); on a first chunk the kernels take both as 0 themselves, so a restart costs no launch.
+ * The key | value cache of a layer is a ring kv [B][R][2D], R >= past_context + n_max, absolute
+ * position p in row p mod R; position 0 stays the phantom key read from the in_proj bias. The
+ * launch holds T rows per slot, row t being step tt = t + *dev_step (dev_step nullable) of the
+ * slot's chunk at sequence position pos[b] + 1 + tt: the encoder runs T = n_max rows at once, the
+ * decoder T = 1 rows n_max times with tt in a device counter. A row is live when tt < the slot's
+ * count. Input of a live row: prev[b] at tt = 0 or when codes is NULL (the decoder, whose prev
+ * encx_ac_decode_slots rewrites every step), codes[b][k][tt-1] + 1 otherwise; a dead row takes
+ * index 0. Only live rows write the ring; a dead row's attention is skipped (context 0). The
+ * arithmetic of a live row is that of encx_lm_input / encx_lm_layer at the same position on a
+ * linear cache, bit for bit (same kernels, same GEMM route, ascending absolute position).
+ * encx_lm_slots_advance: pos[b] = (first ? 0 : pos[b]) + count, and with codes (the encoder)
+ * prev[b][k] = 1 + codes[b][k][count-1]; slots with count 0 keep both. */
+int encx_lm_input_slots(const int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t, int64_t B, int64_t K,
+                        int64_t T, int64_t n_max, const int32_t* slots, const int64_t* pos, const int64_t* prev,
+                        const int64_t* dev_step, const float* emb, int64_t card1, int64_t D, const float* ln_w,
+                        const float* ln_b, float max_period, float* x, encx_stream_t stream);
+int encx_lm_layer_slots(const float* x, float* y, int64_t B, int64_t T, int64_t n_max, float* kv, int64_t R,
+                        const int32_t* slots, const int64_t* pos, const int64_t* dev_step, int64_t past_context,
+                        int64_t D, int64_t heads, int64_t F, const float* in_w, const float* in_b, const float* out_w,
+                        const float* out_b, const float* l1_w, const float* l1_b, const float* l2_w,
+                        const float* l2_b, const float* n1_w, const float* n1_b, const float* n2_w,
+                        const float* n2_b, float* work, encx_stream_t stream);
+int encx_lm_slots_advance(const int32_t* slots, int64_t B, int64_t K, int64_t n_max, int64_t* pos, int64_t* prev,
+                          const int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t, int64_t card1,
+                          encx_stream_t stream);
+/* encx_ac_encode_slots: slot b pushes the first count*K intervals of lohi [B][n_max][K][2]
+ * (encx_lm_heads), flushes, and writes the packet (header byte, payload) at out + b*out_stride;
+ * nbytes[b] = its length (0, nothing written, for count 0), err[b] as encx_ac_encode (2: the
+ * packet needs nbytes[b] > out_stride bytes; 1 + encx_ac_encode_capacity(n_max*K, bits) suffice).
+ * encx_ac_decode_slots: encx_ac_decode's wave per stream for step tt = *dev_step of the chunk, K
+ * symbols against cdf [B][K][card]: active for slots with tt < count and err[b] == 0, a fresh
+ * coder state at tt = 0, payload b at data + b*stride (nbytes[b] bytes). Writes codes[b*c_s +
+ * k*c_k + tt*c_t] (tt < n_max) and prev[b][k] = symbol + 1. err[b] (caller zeroed per packet) as
+ * encx_ac_decode. */
+int encx_ac_encode_slots(const int32_t* lohi, int64_t B, int64_t n_max, int64_t K, const int32_t* slots,
+                         int total_range_bits, uint8_t* out, int64_t out_stride, int64_t* nbytes, int* err,
+                         encx_stream_t stream);
+int encx_ac_decode_slots(const uint8_t* data, int64_t stride, const int64_t* nbytes, int64_t B, int64_t* state,
+                         const int32_t* cdf, int64_t K, int64_t card, int total_range_bits, int64_t* codes,
+                         int64_t c_s, int64_t c_k, int64_t c_t, int64_t n_max, const int64_t* dev_step,
+                         const int32_t* slots, int64_t* prev, int* err, encx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
