@@ -11,6 +11,7 @@
 // encx_bitunpack_slots handle them in one launch too, each slot's count read from the device
 // slot table, one packet (header byte + payload) per slot (encx.h: the packet format).
 #include "common.h"
+#include "prof.h"
 
 namespace {
 
@@ -90,30 +91,12 @@ ENCX_DEV int slot_frames(const int32_t* slots, int b, int n_max) {
     return f < 0 ? 0 : (f > n_max ? n_max : f);
 }
 
-// bitpack_kernel's lane layout per slot, the slot's own n = frames * K values: lane g of slot b
-// owns codes 8g..8g+7 of the slot's t-major sequence and the payload bytes [g*bits, (g+1)*bits)
-// behind the header byte. Lanes past the slot's count leave without forming an address, so the
-// unread tail of a row (columns >= frames) may hold anything. Lane 0 writes the header and the
-// packet length (0 for a slot that sits out: no header either).
-__global__ void bitpack_slots_kernel(const int64_t* __restrict__ codes, int64_t s_b, int64_t s_k, int64_t s_t, int B,
-                                     int K, int n_max, int bits, const int32_t* __restrict__ slots,
-                                     uint8_t* __restrict__ out, int64_t out_stride, int64_t* __restrict__ nbytes,
-                                     int groups, int* __restrict__ err) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= B * groups) return;
-    const int b = j / groups, g = j - b * groups;
-    const int frames = slot_frames(slots, b, n_max);
-    const int n = frames * K;
-    if (g == 0) {
-        nbytes[b] = frames ? 1 + ((int64_t)n * bits + 7) / 8 : 0;
-        if (frames) out[b * out_stride] = (uint8_t)frames;
-    }
-    const int v0 = g * 8;
-    if (v0 >= n) return;
-    const int cnt = n - v0 < 8 ? n - v0 : 8;
+// bitpack_kernel's lane layout over a slot's own sequence of n values (t-major, K codebooks):
+// the lane owns codes v0..v0+cnt-1 (v0 = 8g) and the payload bytes from dst = payload + g*bits.
+// -> the OR of the bits that do not fit. Shared by the fixed-K and the per-slot-K packers.
+ENCX_DEV uint64_t pack_group(const int64_t* __restrict__ src, int64_t s_k, int64_t s_t, int K, int v0, int cnt,
+                             int bits, uint8_t* __restrict__ dst) {
     int t = v0 / K, k = v0 - t * K;
-    const int64_t* src = codes + b * s_b;
-    uint8_t* dst = out + b * out_stride + 1 + (int64_t)g * bits;
     uint64_t acc = 0, bad = 0;
     int nb = 0;
     for (int i = 0; i < cnt; ++i) {
@@ -129,23 +112,14 @@ __global__ void bitpack_slots_kernel(const int64_t* __restrict__ codes, int64_t 
         if (++k == K) { k = 0; ++t; }
     }
     if (nb) *dst = (uint8_t)(acc & 0xff);
-    if (bad) atomicOr(err, 1);
+    return bad;
 }
 
-// The inverse over all n_max * K code positions of every slot: lane g reads its bytes of the
-// payload only where the slot delivers the code, and writes 0 past the slot's count.
-__global__ void bitunpack_slots_kernel(const uint8_t* __restrict__ in, int64_t in_stride, int B, int K, int n_max,
-                                       int bits, const int32_t* __restrict__ slots, int64_t* __restrict__ codes,
-                                       int64_t s_b, int64_t s_k, int64_t s_t, int groups) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= B * groups) return;
-    const int b = j / groups, g = j - b * groups;
-    const int n = slot_frames(slots, b, n_max) * K, total = n_max * K;
-    const int v0 = g * 8;
-    const int cnt = total - v0 < 8 ? total - v0 : 8;
+// The inverse: positions v0..v0+cnt-1 of a (t-major, K) grid; those below n are read from the
+// lane's bytes at src, the others are written as 0.
+ENCX_DEV void unpack_group(const uint8_t* __restrict__ src, int64_t* __restrict__ dst, int64_t s_k, int64_t s_t,
+                           int K, int v0, int cnt, int n, int bits) {
     int t = v0 / K, k = v0 - t * K;
-    const uint8_t* src = in + b * in_stride + (int64_t)g * bits;
-    int64_t* dst = codes + b * s_b;
     const uint64_t mask = (1ull << bits) - 1;
     uint64_t acc = 0;
     int nb = 0;
@@ -165,6 +139,78 @@ __global__ void bitunpack_slots_kernel(const uint8_t* __restrict__ in, int64_t i
     }
 }
 
+// A slot's codebook count from the nq table of a per-slot-bandwidth step, clamped to 0..K.
+ENCX_DEV int slot_nq(const int32_t* nq, int b, int K) {
+    const int q = nq[b];
+    return q < 0 ? 0 : (q > K ? K : q);
+}
+
+// One packet per slot: lane g of slot b owns codes 8g..8g+7 of the slot's t-major sequence of
+// n = frames * K values and the payload bytes [g*bits, (g+1)*bits) behind the header. Lanes past
+// the slot's count leave without forming an address, so the unread tail of a row (columns >=
+// frames) may hold anything. Lane 0 writes the header and the packet length (0 for a slot that
+// sits out: no header either). NQ: K is the slot's own nq[b] (rows >= nq[b] are not read) and
+// the header is two bytes, (frames, K); a slot whose table says nq 0 delivers nothing.
+template <bool NQ>
+__global__ void bitpack_slots_kernel(const int64_t* __restrict__ codes, int64_t s_b, int64_t s_k, int64_t s_t, int B,
+                                     int K, int n_max, int bits, const int32_t* __restrict__ slots,
+                                     const int32_t* __restrict__ nq, uint8_t* __restrict__ out, int64_t out_stride,
+                                     int64_t* __restrict__ nbytes, int groups, int* __restrict__ err) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= B * groups) return;
+    const int b = j / groups, g = j - b * groups;
+    const int Kb = NQ ? slot_nq(nq, b, K) : K;
+    const int frames = Kb ? slot_frames(slots, b, n_max) : 0;
+    const int n = frames * Kb, hdr = NQ ? 2 : 1;
+    if (g == 0) {
+        nbytes[b] = frames ? hdr + ((int64_t)n * bits + 7) / 8 : 0;
+        if (frames) out[b * out_stride] = (uint8_t)frames;
+        if (NQ && frames) out[b * out_stride + 1] = (uint8_t)Kb;
+    }
+    const int v0 = g * 8;
+    if (v0 >= n) return;
+    const uint64_t bad = pack_group(codes + b * s_b, s_k, s_t, Kb, v0, n - v0 < 8 ? n - v0 : 8, bits,
+                                    out + b * out_stride + hdr + (int64_t)g * bits);
+    if (bad) atomicOr(err, 1);
+}
+
+// The inverse over all n_max * K code positions of every slot: lane g reads its bytes of the
+// payload only where the slot delivers the code, and writes 0 past the slot's count.
+__global__ void bitunpack_slots_kernel(const uint8_t* __restrict__ in, int64_t in_stride, int B, int K, int n_max,
+                                       int bits, const int32_t* __restrict__ slots, int64_t* __restrict__ codes,
+                                       int64_t s_b, int64_t s_k, int64_t s_t, int groups) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= B * groups) return;
+    const int b = j / groups, g = j - b * groups;
+    const int n = slot_frames(slots, b, n_max) * K, total = n_max * K;
+    const int v0 = g * 8;
+    unpack_group(in + b * in_stride + (int64_t)g * bits, codes + b * s_b, s_k, s_t, K, v0,
+                 total - v0 < 8 ? total - v0 : 8, n, bits);
+}
+
+// With K per slot: lane g unpacks codes 8g..8g+7 of the slot's own sequence (frames * nq[b]
+// values) into rows < nq[b], then writes the zeros of its share of the [K][n_max] grid: rows >=
+// nq[b] and columns >= frames. The two sets of positions are disjoint.
+__global__ void bitunpack_slots_nq_kernel(const uint8_t* __restrict__ in, int64_t in_stride, int B, int K, int n_max,
+                                          int bits, const int32_t* __restrict__ slots,
+                                          const int32_t* __restrict__ nq, int64_t* __restrict__ codes, int64_t s_b,
+                                          int64_t s_k, int64_t s_t, int groups) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= B * groups) return;
+    const int b = j / groups, g = j - b * groups;
+    const int Kb = slot_nq(nq, b, K);
+    const int frames = Kb ? slot_frames(slots, b, n_max) : 0;
+    const int n = frames * Kb, total = n_max * K;
+    const int v0 = g * 8;
+    int64_t* dst = codes + b * s_b;
+    if (v0 < n)
+        unpack_group(in + b * in_stride + (int64_t)g * bits, dst, s_k, s_t, Kb, v0, n - v0 < 8 ? n - v0 : 8, n, bits);
+    for (int v = v0; v < total && v < v0 + 8; ++v) {
+        const int t = v / K, k = v - t * K;
+        if (t >= frames || k >= Kb) dst[k * s_k + t * s_t] = 0;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -176,9 +222,9 @@ int encx_bitpack_slots(const int64_t* codes, int64_t s_b, int64_t s_k, int64_t s
     ENCX_REQUIRE(B >= 1 && B <= 64 && K >= 1 && K <= 64 && n_max >= 1 && n_max <= 255 && bits >= 1 && bits <= 32);
     ENCX_REQUIRE(out_stride >= 1 + encx_bitpack_bytes(n_max * K, bits));
     const int groups = (int)cdiv(n_max * K, 8);
-    hipLaunchKernelGGL(bitpack_slots_kernel, dim3((unsigned)cdiv(B * groups, 256)), dim3(256), 0,
-                       (hipStream_t)stream, codes, s_b, s_k, s_t, (int)B, (int)K, (int)n_max, bits, slots, out,
-                       out_stride, nbytes, groups, err);
+    hipLaunchKernelGGL(bitpack_slots_kernel<false>, dim3((unsigned)cdiv(B * groups, 256)), dim3(256), 0,
+                       (hipStream_t)stream, codes, s_b, s_k, s_t, (int)B, (int)K, (int)n_max, bits, slots,
+                       (const int32_t*)nullptr, out, out_stride, nbytes, groups, err);
     ENCX_CHECK_LAUNCH();
     return 0;
 }
@@ -193,6 +239,36 @@ int encx_bitunpack_slots(const uint8_t* in, int64_t in_stride, int64_t B, int64_
     hipLaunchKernelGGL(bitunpack_slots_kernel, dim3((unsigned)cdiv(B * groups, 256)), dim3(256), 0,
                        (hipStream_t)stream, in, in_stride, (int)B, (int)K, (int)n_max, bits, slots, codes, s_b, s_k,
                        s_t, groups);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
+
+int encx_bitpack_slots_nq(const int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t, int64_t B, int64_t K,
+                          int64_t n_max, int bits, const int32_t* slots, const int32_t* nq, uint8_t* out,
+                          int64_t out_stride, int64_t* nbytes, int* err, encx_stream_t stream) {
+    ENCX_REQUIRE(codes && slots && nq && out && nbytes && err);
+    ENCX_REQUIRE(B >= 1 && B <= 64 && K >= 1 && K <= 64 && n_max >= 1 && n_max <= 255 && bits >= 1 && bits <= 32);
+    ENCX_REQUIRE(out_stride >= 2 + encx_bitpack_bytes(n_max * K, bits));
+    encx_prof_scope ps((hipStream_t)stream, 0.0, 9.0 * B * K * n_max, "bitpack_slots_nq", false);
+    const int groups = (int)cdiv(n_max * K, 8);
+    hipLaunchKernelGGL(bitpack_slots_kernel<true>, dim3((unsigned)cdiv(B * groups, 256)), dim3(256), 0,
+                       (hipStream_t)stream, codes, s_b, s_k, s_t, (int)B, (int)K, (int)n_max, bits, slots, nq, out,
+                       out_stride, nbytes, groups, err);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
+
+int encx_bitunpack_slots_nq(const uint8_t* in, int64_t in_stride, int64_t B, int64_t K, int64_t n_max, int bits,
+                            const int32_t* slots, const int32_t* nq, int64_t* codes, int64_t s_b, int64_t s_k,
+                            int64_t s_t, encx_stream_t stream) {
+    ENCX_REQUIRE(in && slots && nq && codes);
+    ENCX_REQUIRE(B >= 1 && B <= 64 && K >= 1 && K <= 64 && n_max >= 1 && n_max <= 255 && bits >= 1 && bits <= 32);
+    ENCX_REQUIRE(in_stride >= encx_bitpack_bytes(n_max * K, bits));
+    encx_prof_scope ps((hipStream_t)stream, 0.0, 9.0 * B * K * n_max, "bitunpack_slots_nq", false);
+    const int groups = (int)cdiv(n_max * K, 8);
+    hipLaunchKernelGGL(bitunpack_slots_nq_kernel, dim3((unsigned)cdiv(B * groups, 256)), dim3(256), 0,
+                       (hipStream_t)stream, in, in_stride, (int)B, (int)K, (int)n_max, bits, slots, nq, codes, s_b,
+                       s_k, s_t, groups);
     ENCX_CHECK_LAUNCH();
     return 0;
 }

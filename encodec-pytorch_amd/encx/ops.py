@@ -809,6 +809,88 @@ def rvq_decode(codes, embeds):
     return out
 
 
+def stream_rvq_supports(K: int, bins: int, D: int) -> bool:
+    """Whether the fused streaming quantizer (csrc/stream_rvq.hip) takes K codebooks [bins, D]:
+    1..64 codebooks, bins a multiple of 4 (4..2^20), D a multiple of 8 (8..256). The per-layer
+    kernels take more shapes (any bins, D <= 256); only steps with a per-slot n_q need this one.
+    Host arithmetic only."""
+    return 1 <= K <= 64 and bins % 4 == 0 and 4 <= bins <= 1 << 20 and D % 8 == 0 and 8 <= D <= 256
+
+
+class StreamRVQBooks:
+    """The K_max codebooks of a streaming session as the fused quantizer reads them
+    (csrc/stream_rvq.hip): E [K][bins][D] and, for an encoder (encode=True), its transpose ET
+    [K][D][bins] and ee [K][bins] = |e|^2; a decoder reads only E. prepare() refills the same
+    buffers, so a captured graph sees a weight change."""
+
+    def __init__(self, embeds, encode: bool = True):
+        e0 = embeds[0]
+        _check(e0, 'embed')
+        self.K, (self.bins, self.D) = len(embeds), e0.shape
+        if not stream_rvq_supports(self.K, self.bins, self.D):
+            raise ValueError(f'encx: streaming RVQ of {self.K} codebooks [{self.bins}, {self.D}] '
+                             '(1..64 codebooks, bins a multiple of 4, D a multiple of 8 up to 256)')
+        self.E = torch.empty(self.K, self.bins, self.D, device=e0.device, dtype=torch.float32)
+        self.ET = self.ee = None
+        if encode:
+            self.ET = torch.empty(self.K, self.D, self.bins, device=e0.device, dtype=torch.float32)
+            self.ee = torch.empty(self.K, self.bins, device=e0.device, dtype=torch.float32)
+        self.prepare(embeds)
+
+    @torch.no_grad()
+    def prepare(self, embeds):
+        if len(embeds) != self.K or any(tuple(e.shape) != (self.bins, self.D) for e in embeds):
+            raise ValueError('encx: the codebooks changed shape')
+        for k, e in enumerate(embeds):
+            _check(e, 'embed')
+            call('encx_stream_rvq_prepare', ptr(e.detach().contiguous()), k, self.K, self.bins, self.D,
+                 ptr(self.E), ptr(self.ET), ptr(self.ee), stream())
+
+
+def _tables(books, B, slots, nq):
+    for t, shape, what in ((slots, (B, 2), 'slots'), (nq, (B,), 'nq')):
+        if not t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f'encx: {what} must be a contiguous int32 {list(shape)} tensor on the GPU')
+
+
+def stream_rvq_encode_slots(x, books, slots, nq, codes=None):
+    """The whole residual chain of every slot in ONE launch. x [B, D, n_max] fp32, any strides (a
+    window of the session, read in place); slots int32 [B, 2] (count, first) and nq int32 [B] on
+    the device. Slot b's columns t < count are quantized with its first nq[b] codebooks ->
+    codes [B, K, n_max] int64, zero for k >= nq[b] and t >= count. Bit for bit rvq_encode."""
+    _check(x)
+    B, D, n = x.shape
+    if D != books.D:
+        raise ValueError(f'encx: latent of {D} channels, codebooks of {books.D}')
+    if books.ET is None:
+        raise ValueError('encx: these books were prepared for decoding only (encode=False)')
+    _tables(books, B, slots, nq)
+    if codes is None:
+        codes = torch.empty(B, books.K, n, device=x.device, dtype=torch.int64)
+    call('encx_stream_rvq_encode_slots', x.data_ptr(), *x.stride(), ptr(books.E), ptr(books.ET), ptr(books.ee),
+         B, books.K, books.bins, D, n, ptr(slots), ptr(nq), codes.data_ptr(), *codes.stride(), stream())
+    return codes
+
+
+def stream_rvq_decode_slots(codes, books, slots, nq, out=None):
+    """ONE launch: out[b, :, t] = the sum of slot b's first nq[b] codebook rows at codes[b, k, t]
+    in ascending k (rvq_decode's order), zero for t >= count. codes [B, K, n_max] int64 (rows k >=
+    nq[b] and columns t >= count are not read; a code is clamped to the codebook), out [B, D,
+    n_max] fp32 with any strides (the decoder's first window)."""
+    B, K, n = codes.shape
+    if not codes.is_cuda or codes.dtype != torch.int64 or K != books.K:
+        raise ValueError(f'encx: expected int64 codes [B, {books.K}, n] on the GPU')
+    _tables(books, B, slots, nq)
+    if out is None:
+        out = torch.empty(B, books.D, n, device=codes.device, dtype=torch.float32)
+    if tuple(out.shape) != (B, books.D, n):
+        raise ValueError(f'encx: out must be [{B}, {books.D}, {n}]')
+    _check(out, 'out')
+    call('encx_stream_rvq_decode_slots', codes.data_ptr(), *codes.stride(), ptr(books.E), B, K, books.bins,
+         books.D, n, ptr(slots), ptr(nq), out.data_ptr(), *out.stride(), stream())
+    return out
+
+
 # ---------------------------------------------------------------------------- LSTM
 class LSTMFn(torch.autograd.Function):
     """SLSTM.forward (modules/lstm.py:22-28): torch.nn.LSTM(H, H, L) over [T, B, H] + skip.

@@ -43,8 +43,28 @@ length costs: every layer is causal, so the columns past a slot's count influenc
 carried, and only the two places that carry state look at the per-slot counts (a slot table in
 device memory, read by the kernels): the window roll / first-chunk fill and the LSTM's h and c
 (csrc/stream.hip). encode(x) / decode(codes) are the uniform case. A slot's results are
-bit-identical to the same stream alone in a session of one. Not supported: a bandwidth (n_q) per
-slot, more than 64 slots, an `.ecdc` container for live streams.
+bit-identical to the same stream alone in a session of one. Not supported: more than 64 slots,
+an `.ecdc` container for live streams.
+
+Bandwidth per slot. One model serves every bandwidth by keeping the first n_q codebooks, and no
+state a session carries depends on n_q, so every slot may use its own count, and change it from
+one step to the next:
+
+    enc = StreamEncoder(model, 64, n_q=32)            # the session's largest count (24 kbps)
+    dec = StreamDecoder(model, 64, n_q=32)
+    nq = [enc.n_q_for(6.0)] * 64                      # per slot and step, 1..enc.n_q
+    codes = enc.encode_slots(x, frames, n_q=nq)       # [B, 32, n_max], rows k >= nq[b] zero
+    wav = dec.decode_slots(codes, frames, n_q=nq)     # rows k >= nq[b] are not read
+
+The counts live in a device table beside the slot table, so one captured graph serves every mix.
+The quantizer of such a step is one launch for all slots and layers (csrc/stream_rvq.hip): a
+column's whole residual chain runs in one workgroup with n_q[b] as its loop bound, and the codes
+are, bit for bit, rows [:n_q[b]] of the codes at the session's full bandwidth. Packets of such a
+step carry a second header byte with K (StreamPacker / StreamUnpacker(..., slot_n_q=True));
+their LM-coded form is not supported. The fused quantizer takes codebooks of bins a multiple
+of 4 and a latent dimension a multiple of 8 (up to 256); a session of any other model is built
+and streams as before, and only its steps that pass n_q are refused (NotImplementedError, a
+host check: check_rvq_shape).
 
 Packets. What goes on the wire is one self-contained packet per delivering slot and step
 (`StreamPacker` / `StreamUnpacker`; the format is documented in include/encx.h): a header byte
@@ -265,6 +285,31 @@ def check_frames(started: tp.Sequence[bool], frames, min_first_frames: int, max_
     return max(frames), any_first
 
 
+def check_n_q(frames, n_q, n_q_max: int) -> tp.List[int]:
+    """n_q[b] = the codebooks slot b uses this step: an int in 1..n_q_max for a slot that delivers
+    frames; whatever stands at a slot with 0 frames is ignored. -> the table the kernels read, with
+    0 at the slots that sit out. Raises ValueError; host data only."""
+    try:
+        n_q = list(n_q)
+    except TypeError:
+        raise ValueError('encx streaming: n_q must be a sequence of ints') from None
+    if len(n_q) != len(frames):
+        raise ValueError(f'encx streaming: n_q for {len(n_q)} slots, the step has {len(frames)}')
+    out = []
+    for b, (f, q) in enumerate(zip(frames, n_q)):
+        if not f:
+            out.append(0)
+            continue
+        try:
+            q = operator.index(q)
+        except TypeError:
+            raise ValueError(f'encx streaming: n_q of slot {b} is not an int') from None
+        if not 1 <= q <= n_q_max:
+            raise ValueError(f'encx streaming: n_q {q} in slot {b} (1..{n_q_max})')
+        out.append(q)
+    return out
+
+
 def check_restart(slots, batch: int) -> tp.List[int]:
     """The slot indices of a restart(), each in 0..batch-1 (ValueError otherwise)."""
     slots = _ints(slots, 'slots')
@@ -332,6 +377,14 @@ class _Session:
                          for _ in range(4)]
         self._staged = 0
         self._slot_graphs: tp.Dict[tuple, tuple] = {}
+        # the codebook count per slot (encx.h: nq[B]) of a per-slot-bandwidth step, beside the slot
+        # table and uploaded the same way; its graphs never replace one of the paths above
+        self._nq = torch.zeros(self.B, device=dev, dtype=torch.int32)
+        self._nq_host: tp.Optional[tuple] = None
+        self._nq_staging = [(torch.zeros(self.B, dtype=torch.int32).pin_memory(), torch.cuda.Event())
+                            for _ in range(4)]
+        self._nq_staged = 0
+        self._nq_graphs: tp.Dict[tuple, tuple] = {}
         self._cols = torch.arange(max(self._W), device=dev, dtype=torch.int32)
         self._slot_tab = self._slot_table()
         self.refresh_weights()
@@ -404,6 +457,20 @@ class _Session:
         self._slots.copy_(buf, non_blocking=True)
         ev.record()
         self._slots_host = tab
+
+    def put_nq(self, n_q):
+        """Fill the device nq table (a check_n_q result) for this step, as put_slots: only when it
+        changed, through rotating pinned staging."""
+        tab = tuple(int(q) for q in n_q)
+        if tab == self._nq_host:
+            return
+        buf, ev = self._nq_staging[self._nq_staged]
+        self._nq_staged = (self._nq_staged + 1) % len(self._nq_staging)
+        ev.synchronize()
+        buf.copy_(torch.tensor(tab, dtype=torch.int32))
+        self._nq.copy_(buf, non_blocking=True)
+        ev.record()
+        self._nq_host = tab
 
     def keep(self, cols, rate):
         """[B, 1, cols] bool, from the slot table on the device (capturable): the columns of a
@@ -527,11 +594,12 @@ class _Session:
         self._fresh = False
         return out
 
-    def _step_slots(self, frames, n_max, any_first, body):
+    def _step_slots(self, frames, n_max, any_first, body, graphs=None, extra=()):
         """A step under the slot table (already filled: put_slots): body(n_max, any_first), keyed
         (n_max, any_first). The table is read by the kernels, so one graph serves whichever slots
-        join, sit out or deliver fewer frames."""
-        out = self._run(self._slot_graphs, (n_max, any_first), body)
+        join, sit out or deliver fewer frames. graphs / extra: another set of graphs and further
+        key parts (the per-slot-bandwidth steps)."""
+        out = self._run(self._slot_graphs if graphs is None else graphs, (n_max, any_first) + tuple(extra), body)
         for b, f in enumerate(frames):
             if f:
                 self.started[b] = True
@@ -555,6 +623,39 @@ class _Session:
         self.reset()
 
 
+def _warm_nq(s: _Session, n_q: int, body, extra=()):
+    """Load the kernels of a per-slot-bandwidth step before any capture, as _warm does: one first
+    chunk and one later chunk of a single frame (the quantizer's one-column tiling) on the zero
+    state, eagerly; then back to a clean session."""
+    graphs, s.graphs = s.graphs, False
+    try:
+        s.put_nq([n_q] * s.B)
+        for n in (s.min_first_frames, 1):
+            frames = [n] * s.B
+            s.put_slots(frames)
+            s._step_slots(frames, *s.check_frames(frames), body, s._nq_graphs, extra)
+    finally:
+        s.graphs = graphs
+    s.reset()
+
+
+def check_rvq_shape(n_q: int, bins: int, D: int):
+    """A step with a per-slot n_q runs the fused quantizer, which takes fewer codebook shapes
+    than the per-layer kernels of every other step (ops.stream_rvq_supports). Raises
+    NotImplementedError; host arithmetic only, so a session of any model the per-layer path
+    streams is still built, and only its steps that pass n_q are refused."""
+    if not ops.stream_rvq_supports(n_q, bins, D):
+        _refuse(f'a per-slot n_q with {n_q} codebooks of {bins} x {D} (at most 64 codebooks, bins a multiple '
+                'of 4, a latent dimension that is a multiple of 8 up to 256); steps without n_q run')
+
+
+def _books(embeds, encode):
+    """The packed codebooks of the fused quantizer, or None where it does not take their shape
+    (check_rvq_shape then refuses the steps that would need them)."""
+    bins, D = embeds[0].shape
+    return ops.StreamRVQBooks(embeds, encode) if ops.stream_rvq_supports(len(embeds), bins, D) else None
+
+
 def _embeds(model, n_q):
     layers = model.quantizer.vq.layers
     if not 1 <= n_q <= len(layers):
@@ -564,16 +665,24 @@ def _embeds(model, n_q):
 
 class StreamEncoder:
     """Chunked encoder of a causal model for `batch` streams: encode(x [B, C, n*hop]) -> codes
-    [B, n_q, n] (int64), n_q from model.bandwidth at construction. See the module docstring."""
+    [B, n_q, n] (int64). n_q, the session's codebook count (the largest a slot may use with a
+    per-slot n_q), is the constructor's argument or, by default, follows from model.bandwidth. See
+    the module docstring."""
 
-    def __init__(self, model, batch: int, max_frames: int = 8, graphs: bool = True):
+    def __init__(self, model, batch: int, max_frames: int = 8, graphs: bool = True, n_q: tp.Optional[int] = None):
         plan = encoder_plan(model)
-        self.n_q = model.quantizer.get_num_quantizers_for_bandwidth(model.frame_rate, model.bandwidth)
+        if n_q is None:
+            n_q = model.quantizer.get_num_quantizers_for_bandwidth(model.frame_rate, model.bandwidth)
+        self.n_q = operator.index(n_q)  # the session's largest codebook count
+        _embeds(model, self.n_q)        # refused here, before any device call
         self._s = _Session(model, plan, batch, max_frames, graphs)
         self.channels = model.channels
         self._embeds = _embeds(model, self.n_q)
+        self._books = _books(self._embeds, True)
         with torch.no_grad():
             self._s._warm(self._body, self._body_slots)
+            if self._books is not None:
+                _warm_nq(self._s, self.n_q, self._body_nq, (False,))
 
     hop_length = property(lambda self: self._s.hop_length)
     min_first_frames = property(lambda self: self._s.min_first_frames)
@@ -590,6 +699,29 @@ class StreamEncoder:
     def refresh_weights(self):
         self._s.refresh_weights()
         self._embeds = _embeds(self._s.model, self.n_q)
+        if self._books is not None:
+            self._books.prepare(self._embeds)
+
+    def n_q_for(self, bandwidth_kbps: float) -> int:
+        """The codebook count of this model at a bandwidth (kbps), for encode_slots(n_q=...).
+        ValueError when the session was built for fewer codebooks."""
+        m = self._s.model
+        q = m.quantizer.get_num_quantizers_for_bandwidth(m.frame_rate, bandwidth_kbps)
+        if q > self.n_q:
+            raise ValueError(f'encx streaming: {bandwidth_kbps} kbps needs {q} codebooks, the session has {self.n_q}')
+        return q
+
+    def _body_nq(self, n, first, latent):
+        """A slots step whose quantizer is the fused kernel under the nq table: the latent is read
+        in place from the last window, all slots and layers in one launch."""
+        s = self._s
+        s._layers(n, first, slots=True)
+        dst = s.plan.layers[-1].dst
+        win = s.bufs[dst][:, :, s.plan.windows[dst].P:][:, :, :n]
+        codes = ops.stream_rvq_encode_slots(win, self._books, s._slots, s._nq)
+        if not latent:
+            return (codes,)
+        return codes, torch.where(s.keep(n, 1), win, 0.).contiguous()
 
     def _body(self, n, first):
         s = self._s
@@ -632,21 +764,35 @@ class StreamEncoder:
         return (codes, emb) if return_latent else codes
 
     @torch.no_grad()
-    def encode_slots(self, x: torch.Tensor, frames: tp.Sequence[int], return_latent: bool = False):
+    def encode_slots(self, x: torch.Tensor, frames: tp.Sequence[int], return_latent: bool = False,
+                     n_q: tp.Optional[tp.Sequence[int]] = None):
         """x [B, C, n_max * hop_length], frames[b] = the frames slot b delivers (0: it sits out),
         n_max = max(frames) -> codes [B, n_q, n_max] (and the latent [B, D, n_max]). Slot b's
         samples past frames[b] * hop_length are not read; its result columns past frames[b] are
-        zero. Each slot equals the same stream alone."""
+        zero. Each slot equals the same stream alone.
+
+        n_q: B ints, the codebooks each slot uses THIS step (1..self.n_q for a slot that delivers
+        frames; ignored for the others); it may differ from the slot's last step, which is how a
+        stream changes bandwidth. Rows k >= n_q[b] of slot b's codes are zero, rows k < n_q[b] are
+        those of the session's full bandwidth (code k depends only on layers < k). The quantizer
+        then runs as one launch for all slots and layers (csrc/stream_rvq.hip)."""
         s = self._s
         n = self._samples(x)
         frames = _ints(frames, 'frames')
         n_max, any_first = s.check_frames(frames)
         if n != n_max:
             raise ValueError(f'encx streaming: {n} frames of samples for max(frames) = {n_max}')
+        if n_q is not None:
+            check_rvq_shape(self.n_q, *self._embeds[0].shape)
+            n_q = check_n_q(frames, n_q, self.n_q)
         ops._check(x)
         s.put_slots(frames)
         P = s.plan.windows[0].P
         s.bufs[0][:, :, P:P + x.shape[2]].copy_(torch.where(s.keep(x.shape[2], s.hop_length), x, 0.))
+        if n_q is not None:
+            s.put_nq(n_q)
+            out = s._step_slots(frames, n_max, any_first, self._body_nq, s._nq_graphs, (bool(return_latent),))
+            return out if return_latent else out[0]
         codes, emb = s._step_slots(frames, n_max, any_first, self._body_slots)
         return (codes, emb) if return_latent else codes
 
@@ -665,8 +811,12 @@ class StreamDecoder:
         self.bins = model.quantizer.bins
         self._embeds = _embeds(model, self.n_q)
         self._codes: tp.Dict[int, torch.Tensor] = {}
+        self._codes_nq: tp.Dict[int, torch.Tensor] = {}
+        self._books = _books(self._embeds, False)  # a decoder gathers rows: no transpose, no |e|^2
         with torch.no_grad():
             self._s._warm(self._body, self._body_slots)
+            if self._books is not None:
+                _warm_nq(self._s, self.n_q, self._body_nq)
 
     hop_length = property(lambda self: self._s.hop_length)
     min_first_frames = property(lambda self: self._s.min_first_frames)
@@ -682,6 +832,26 @@ class StreamDecoder:
     def refresh_weights(self):
         self._s.refresh_weights()
         self._embeds = _embeds(self._s.model, self.n_q)
+        if self._books is not None:
+            self._books.prepare(self._embeds)
+
+    def _code_buf_nq(self, n):
+        """The codes of a per-slot-bandwidth step as the caller passed them, [B, n_q, n]: the
+        kernel clamps them and reads neither a slot's tail nor its rows k >= n_q[b]."""
+        c = self._codes_nq.get(n)
+        if c is None:
+            c = self._codes_nq[n] = torch.zeros(self._s.B, self.n_q, n, device=self._s.dev, dtype=torch.int64)
+        return c
+
+    def _body_nq(self, n, first):
+        """A slots step whose dequantizer is the fused kernel under the nq table, written straight
+        into the first window behind its history."""
+        s = self._s
+        P = s.plan.windows[0].P
+        ops.stream_rvq_decode_slots(self._code_buf_nq(n), self._books, s._slots, s._nq, s.bufs[0][:, :, P:P + n])
+        s._layers(n, first, slots=True)
+        out = s.bufs[s.plan.layers[-1].dst][:, :, :n * s.hop_length]
+        return (torch.where(s.keep(n * s.hop_length, s.hop_length), out, 0.).contiguous(),)
 
     def _code_buf(self, n):
         c = self._codes.get(n)
@@ -734,20 +904,32 @@ class StreamDecoder:
         return s._step(n, self._body)[0]
 
     @torch.no_grad()
-    def decode_slots(self, codes: torch.Tensor, frames: tp.Sequence[int]) -> torch.Tensor:
+    def decode_slots(self, codes: torch.Tensor, frames: tp.Sequence[int],
+                     n_q: tp.Optional[tp.Sequence[int]] = None) -> torch.Tensor:
         """codes [B, n_q, n_max], frames[b] = the frames slot b delivers (0: it sits out), n_max =
         max(frames) -> wav [B, C, n_max * hop_length]. Slot b's codes past frames[b] are not read
         (code 0 is decoded in their place); its samples past frames[b] * hop_length are zero.
-        Each slot equals the same stream alone."""
+        Each slot equals the same stream alone.
+
+        n_q: as StreamEncoder.encode_slots: B ints, the codebooks of each slot this step; rows
+        k >= n_q[b] of slot b's codes are not read, and the slot's wave is that of a decoder built
+        for n_q[b] codebooks."""
         s = self._s
         n = self._frames(codes)
         frames = _ints(frames, 'frames')
         n_max, any_first = s.check_frames(frames)
         if n != n_max:
             raise ValueError(f'encx streaming: {n} frames of codes for max(frames) = {n_max}')
+        if n_q is not None:
+            check_rvq_shape(self.n_q, *self._embeds[0].shape)
+            n_q = check_n_q(frames, n_q, self.n_q)
         if not codes.is_cuda:
             raise RuntimeError('encx streaming takes device tensors (no CPU fallback)')
         s.put_slots(frames)
+        if n_q is not None:
+            s.put_nq(n_q)
+            self._code_buf_nq(n).copy_(codes)
+            return s._step_slots(frames, n_max, any_first, self._body_nq, s._nq_graphs)[0]
         buf = self._code_buf(n)
         # clamped as in decode(); past a slot's count whatever the caller left becomes code 0
         buf.copy_(torch.where(s.keep(n, 1).squeeze(1), codes.permute(1, 0, 2).clamp(0, self.bins - 1), 0))
@@ -763,12 +945,23 @@ def packet_bytes(n: int, K: int, bits: int) -> int:
     return 1 + (n * K * bits + 7) // 8
 
 
+def packet_bytes_nq(n: int, K: int, bits: int) -> int:
+    """Length of a variable-bandwidth packet of n frames of K codes: the two header bytes (n, K)
+    and ceil(n K bits / 8)."""
+    return 2 + (n * K * bits + 7) // 8
+
+
 class _Packets:
     """What StreamPacker and StreamUnpacker share: the arguments, the LM session behind the
     LM-coded form, and for the raw form a slot table and byte buffers on the device, made at the
-    first valid step (every refusal of a step's arguments is a pure host check)."""
+    first valid step (every refusal of a step's arguments is a pure host check). slot_n_q: the
+    variable-bandwidth packets (two header bytes, K per slot from an nq table); n_q is then the
+    largest K."""
 
-    def __init__(self, model, batch, n_q, use_lm, lm, max_frames, graphs, lm_session):
+    def __init__(self, model, batch, n_q, use_lm, lm, max_frames, graphs, lm_session, slot_n_q=False):
+        if use_lm and slot_n_q:
+            _refuse('LM-coded packets with a per-slot n_q (use_lm=True with slot_n_q=True)')
+        self.slot_n_q = bool(slot_n_q)
         if not 1 <= batch <= MAX_BATCH:
             raise ValueError(f'encx streaming: batch {batch} (1..{MAX_BATCH})')
         if not 1 <= n_q <= min(model.quantizer.n_q, 64):
@@ -801,8 +994,10 @@ class _Packets:
             if dev.type != 'cuda':
                 raise RuntimeError('encx streaming runs on the GPU (no CPU fallback): move the model first')
             ensure_device(dev)
-            self._stride = packet_bytes(self.max_frames, self.n_q, self.bits)
+            self._stride = (packet_bytes_nq if self.slot_n_q else packet_bytes)(self.max_frames, self.n_q, self.bits)
             self._slots = torch.zeros(self.B, 2, dtype=torch.int32, device=dev)
+            self._nq = torch.zeros(self.B, dtype=torch.int32, device=dev)
+            self._nq_tab = None
             self._bytes = torch.zeros(self.B, self._stride, dtype=torch.uint8, device=dev)
             self._nbytes = torch.zeros(self.B, dtype=torch.int64, device=dev)
             self._err = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -817,6 +1012,13 @@ class _Packets:
             self._slots.copy_(torch.tensor(tab, dtype=torch.int32))
             self._tab = tab
 
+    def _put_nq(self, n_q):
+        """The nq table of a variable-bandwidth step, uploaded only when it changed."""
+        tab = [int(q) for q in n_q]
+        if tab != self._nq_tab:
+            self._nq.copy_(torch.tensor(tab, dtype=torch.int32))
+            self._nq_tab = tab
+
 
 class StreamPacker(_Packets):
     """The codes of a slots step as one self-contained packet per delivering slot:
@@ -830,16 +1032,24 @@ class StreamPacker(_Packets):
     packet format is documented in include/encx.h. Slot b's codes past frames[b] are not read."""
 
     def __init__(self, model, batch: int, n_q: int, use_lm: bool = False, lm=None, max_frames: int = 8,
-                 graphs: bool = True):
+                 graphs: bool = True, slot_n_q: bool = False):
         from .lm import LMStreamEncoder
-        super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamEncoder)
+        super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamEncoder, slot_n_q)
 
     @torch.no_grad()
-    def pack_slots(self, codes: torch.Tensor, frames: tp.Sequence[int]) -> tp.List[bytes]:
+    def pack_slots(self, codes: torch.Tensor, frames: tp.Sequence[int],
+                   n_q: tp.Optional[tp.Sequence[int]] = None) -> tp.List[bytes]:
+        """slot_n_q=True: pack_slots(codes, frames, n_q) -> variable-bandwidth packets (include/encx.h):
+        bytes (frames[b], n_q[b]) and the payload of codes[b, :n_q[b], :frames[b]]; rows k >= n_q[b]
+        are not read."""
+        if self.slot_n_q != (n_q is not None):
+            raise ValueError('encx streaming: n_q goes with slot_n_q=True, and only with it')
         if self._lm is not None:
             return self._lm.packets(codes, frames)
         frames = _ints(frames, 'frames')
         n_max, _ = check_frames([True] * self.B, frames, 1, self.max_frames)
+        if n_q is not None:
+            n_q = check_n_q(frames, n_q, self.n_q)
         if codes.dim() != 3 or tuple(codes.shape) != (self.B, self.n_q, n_max) or codes.dtype != torch.int64:
             raise ValueError(f'encx streaming: expected int64 codes [{self.B}, {self.n_q}, max(frames) = {n_max}], '
                              f'got {codes.dtype} {tuple(codes.shape)}')
@@ -849,6 +1059,16 @@ class StreamPacker(_Packets):
         self._put_slots(frames)
         self._err.zero_()
         sb, sk, s_t = codes.stride()
+        if n_q is not None:
+            self._put_nq(n_q)
+            call('encx_bitpack_slots_nq', codes.data_ptr(), sb, sk, s_t, self.B, self.n_q, n_max, self.bits,
+                 self._slots.data_ptr(), self._nq.data_ptr(), self._bytes.data_ptr(), self._stride,
+                 self._nbytes.data_ptr(), self._err.data_ptr(), stream())
+            host = self._bytes.cpu()
+            if int(self._err.item()):
+                raise ValueError(f'encx streaming: a delivered code does not fit in {self.bits} bits')
+            return [host[b, :packet_bytes_nq(f, q, self.bits)].numpy().tobytes() if f else b''
+                    for b, (f, q) in enumerate(zip(frames, n_q))]
         call('encx_bitpack_slots', codes.data_ptr(), sb, sk, s_t, self.B, self.n_q, n_max, self.bits,
              self._slots.data_ptr(), self._bytes.data_ptr(), self._stride, self._nbytes.data_ptr(),
              self._err.data_ptr(), stream())
@@ -866,9 +1086,9 @@ class StreamUnpacker(_Packets):
     and zero codes, is listed in `failed`, and refuses packets until restart([b])."""
 
     def __init__(self, model, batch: int, n_q: int, use_lm: bool = False, lm=None, max_frames: int = 8,
-                 graphs: bool = True):
+                 graphs: bool = True, slot_n_q: bool = False):
         from .lm import LMStreamDecoder
-        super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamDecoder)
+        super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamDecoder, slot_n_q)
 
     @property
     def failed(self) -> tp.List[int]:
@@ -893,8 +1113,57 @@ class StreamUnpacker(_Packets):
             raise ValueError('encx streaming: no slot delivers a frame')
         return frames
 
+    def _headers_nq(self, packets):
+        """The (n, K) headers of variable-bandwidth packets -> (frames, n_q), 0 and 0 for b''."""
+        if len(packets) != self.B:
+            raise ValueError(f'encx streaming: packets for {len(packets)} slots, the session has {self.B}')
+        frames, n_q = [], []
+        for b, p in enumerate(packets):
+            if not isinstance(p, (bytes, bytearray)):
+                raise ValueError(f'encx streaming: the packet of slot {b} is not bytes')
+            n, K = (p[0], p[1]) if len(p) >= 2 else (0, 0)
+            if len(p):
+                if len(p) < 2:
+                    raise ValueError(f'encx streaming: the packet of slot {b} has no (n, K) header')
+                if not 1 <= n <= self.max_frames:
+                    raise ValueError(f'encx streaming: the packet of slot {b} announces {n} frames '
+                                     f'(1..max_frames={self.max_frames})')
+                if not 1 <= K <= self.n_q:
+                    raise ValueError(f'encx streaming: the packet of slot {b} announces {K} codebooks '
+                                     f'(1..n_q={self.n_q})')
+                if len(p) != packet_bytes_nq(n, K, self.bits):
+                    raise ValueError(f'encx streaming: a packet of {n} frames of {K} codebooks in slot {b} has '
+                                     f'{packet_bytes_nq(n, K, self.bits)} bytes, not {len(p)}')
+            frames.append(int(n))
+            n_q.append(int(K))
+        if not any(frames):
+            raise ValueError('encx streaming: no slot delivers a frame')
+        return frames, n_q
+
+    def _upload(self, packets):
+        host = torch.zeros(self.B, self._stride, dtype=torch.uint8)
+        for b, p in enumerate(packets):
+            if len(p):
+                host[b, :len(p)] = torch.frombuffer(bytearray(p), dtype=torch.uint8)
+        self._bytes.copy_(host)
+
     @torch.no_grad()
     def unpack_slots(self, packets: tp.Sequence[bytes]):
+        """slot_n_q=True: -> (codes [B, n_q, max(frames)], frames, n_q) from variable-bandwidth
+        packets, n_q[b] = 0 for an empty packet and zero rows at k >= n_q[b]: ready for
+        StreamDecoder.decode_slots(codes, frames, n_q)."""
+        if self.slot_n_q:
+            frames, n_q = self._headers_nq(packets)
+            n_max = max(frames)
+            self._ensure()
+            self._upload(packets)
+            self._put_slots(frames)
+            self._put_nq(n_q)
+            codes = torch.empty(self.B, self.n_q, n_max, dtype=torch.int64, device=self._dev)
+            sb, sk, s_t = codes.stride()
+            call('encx_bitunpack_slots_nq', self._bytes.data_ptr() + 2, self._stride, self.B, self.n_q, n_max,
+                 self.bits, self._slots.data_ptr(), self._nq.data_ptr(), codes.data_ptr(), sb, sk, s_t, stream())
+            return codes, frames, n_q
         frames = self._headers(packets)
         if self._lm is not None:
             codes, failed = self._lm.decode_slots([bytes(p[1:]) for p in packets], frames)

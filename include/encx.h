@@ -856,6 +856,68 @@ int encx_bitpack_slots(const int64_t* codes, int64_t s_b, int64_t s_k, int64_t s
 int encx_bitunpack_slots(const uint8_t* in, int64_t in_stride, int64_t B, int64_t K, int64_t n_max, int bits,
                          const int32_t* slots, int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t,
                          encx_stream_t stream);
+
+/* ------------------------------------------- a bandwidth (n_q) per slot and step (encx/streaming.py)
+ * One model serves every bandwidth by keeping the first n_q codebooks, and nothing a session carries
+ * depends on n_q, so each slot of a step may use its own count, and change it from step to step. A
+ * second device table beside the slot table, int32 nq[B], holds the counts: nq[b] codebooks for slot
+ * b this step, clamped by every kernel to 0..K_max (K_max: the session's largest count; rows k >=
+ * nq[b] of a slot's codes are written as 0 by the producers and never read by the consumers). Both
+ * tables are read on the device, so a captured graph serves every mix of bandwidths.
+ *
+ * VARIABLE-BANDWIDTH PACKET. As the raw packet above with a two-byte header:
+ *   byte 0     n  (1..255 latent frames)
+ *   byte 1     K  (1..64 codebooks, at most the receiving session's K_max)
+ *   payload    the n*K codes, t-major then codebook, `bits` bits each: encx_bitpack_bytes(n*K, bits)
+ *              bytes, byte for byte the payload of a one-byte-header raw packet of K codebooks.
+ * The one-byte-header packet stays the default; there is no LM-coded form with a per-slot K.
+ *
+ * The quantizer itself runs as ONE launch per direction (csrc/stream_rvq.hip): columns are
+ * independent and code k depends only on layers < k, so a column's whole residual chain runs inside
+ * one workgroup with nq[b] as its loop bound. bins a multiple of 4 (4..2^20), D a multiple of 8
+ * (8..256), B and K_max 1..64, n_max 1..255; anything else, or a NULL pointer, is ENCX_EINVAL before
+ * any launch.
+ *
+ * encx_stream_rvq_prepare: layer k (0..K_max-1) of the session's codebooks, embed [bins][D], into
+ * packed [K_max][bins][D], its transpose packed_t [K_max][D][bins] (the distance loop reads along
+ * the codes) and ee [K_max][bins] = |e|^2 as the ascending-d fmaf chain from 0 of encx_rvq_argmin.
+ * One launch per layer, at construction and after a weight change. packed_t and ee may both be
+ * NULL (a decoder reads only packed); one of them alone is ENCX_EINVAL.
+ * encx_stream_rvq_encode_slots: the latent x[b*x_b + d*x_d + t*x_t] read in place (a window of the
+ * session), columns t < count of slot b only; codes[b*c_b + k*c_k + t*c_t] (int64) for k < nq[b],
+ * 0 for k >= nq[b] and for t >= count (all K_max rows and n_max columns are written). The codes are
+ * bit for bit those of encx_rvq_argmin + encx_rvq_apply (ste 0) layer by layer: distance (|x|^2 - 2
+ * x.e) + |e|^2 with x.e one fmaf chain in ascending d (bitwise the v_mfma_f32_32x32x2_f32 chain),
+ * argmin over ord_key(v) << 32 | code (ties to the lowest code), residual x - e exactly. No element's
+ * reduction order depends on B, n_max, the other slots or the tile its column lands in (two columns
+ * per workgroup, one when n_max is 1).
+ * encx_stream_rvq_decode_slots: out[b*o_b + d*o_d + t*o_t] = ((e_0[c_0] + e_1[c_1]) + ...)[d] over
+ * k < nq[b] in ascending k (encx_rvq_gather's order), codes clamped to 0..bins-1, 0 for t >= count;
+ * written straight into the decoder's first window. Rows k >= nq[b] and columns t >= count of codes
+ * are not read.
+ * encx_bitpack_slots_nq / encx_bitunpack_slots_nq: encx_bitpack_slots / encx_bitunpack_slots with K
+ * per slot from nq[b] (K is then the row count of codes and the largest K): the packer writes the
+ * two-byte header and nbytes[b] = 2 + encx_bitpack_bytes(count*nq[b], bits), 0 for a slot that
+ * delivers nothing (out_stride >= 2 + encx_bitpack_bytes(n_max*K, bits)); the unpacker takes the
+ * PAYLOAD (the host has put the header's n and K into the two tables) and writes all K rows and
+ * n_max columns, 0 for k >= nq[b] and t >= count. */
+int encx_stream_rvq_prepare(const float* embed, int64_t k, int64_t K_max, int64_t bins, int64_t D, float* packed,
+                            float* packed_t, float* ee, encx_stream_t stream);
+int encx_stream_rvq_encode_slots(const float* x, int64_t x_b, int64_t x_d, int64_t x_t, const float* packed,
+                                 const float* packed_t, const float* ee, int64_t B, int64_t K_max, int64_t bins,
+                                 int64_t D, int64_t n_max, const int32_t* slots, const int32_t* nq, int64_t* codes,
+                                 int64_t c_b, int64_t c_k, int64_t c_t, encx_stream_t stream);
+int encx_stream_rvq_decode_slots(const int64_t* codes, int64_t c_b, int64_t c_k, int64_t c_t, const float* packed,
+                                 int64_t B, int64_t K_max, int64_t bins, int64_t D, int64_t n_max,
+                                 const int32_t* slots, const int32_t* nq, float* out, int64_t o_b, int64_t o_d,
+                                 int64_t o_t, encx_stream_t stream);
+int encx_bitpack_slots_nq(const int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t, int64_t B, int64_t K,
+                          int64_t n_max, int bits, const int32_t* slots, const int32_t* nq, uint8_t* out,
+                          int64_t out_stride, int64_t* nbytes, int* err, encx_stream_t stream);
+int encx_bitunpack_slots_nq(const uint8_t* in, int64_t in_stride, int64_t B, int64_t K, int64_t n_max, int bits,
+                            const int32_t* slots, const int32_t* nq, int64_t* codes, int64_t s_b, int64_t s_k,
+                            int64_t s_t, encx_stream_t stream);
+
 /* The LM over slots. Device state per slot: pos[b] (int64, frames coded so far) and prev[b][K]
  * (int64, the LM input index of the slot's next row: 1 + its last code, 0 at the start of a
  * stream); on a first chunk the kernels take both as 0 themselves, so a restart costs no launch.

@@ -18,7 +18,11 @@ slots_section) and writes profiles/stream/stream_bench_slots.json; there the rea
 is the join step's encode plus decode against the frame period.
 
 python tools/stream_bench.py [--batches 1,16,64] [--frames 1,4] [--rounds 5] [--out FILE]
+--nq measures a bandwidth (n_q) per slot (nq_section: the fused quantizer against the step without
+n_q) and writes profiles/stream/stream_bench_nq.json.
+
 python tools/stream_bench.py --slots [--rounds 5] [--slots-out FILE]
+python tools/stream_bench.py --nq [--rounds 5] [--nq-out FILE]
 """
 import argparse
 import json
@@ -91,8 +95,76 @@ def slots_section(args, torch, m, dev, hop, period_ms, measure, B=64, join=7):
                           'frame_period_ms': round(period_ms, 4), 'met': join_ms < period_ms}}
 
 
+def nq_section(args, torch, m, dev, hop, timed, B=64):
+    """A bandwidth (n_q) per slot at B = 64, n = 1 and 8 frames per step, K_max = 8 and 32, eager
+    and graph replay, encode step and decode step apart:
+      a   encode_slots / decode_slots with n_q = K_max for every slot (the fused quantizer);
+      b   the same with the slots cycling through 2, 4, 8, .., K_max codebooks;
+      c   encode_slots / decode_slots without n_q at K_max (the per-layer quantizer kernels).
+    The three run alternately, round by round, in one process (each round is one block of steps
+    per case). The quantizer alone (q_*: the step's [B, 128, n] latent, launched back to back) is
+    timed in the eager rounds."""
+    from encx.streaming import StreamEncoder, StreamDecoder
+    rows = []
+    for K in (8, 32):
+        ladder = [k for k in (2, 4, 8, 16, 32, 64) if k <= K]
+        full, mixed = [K] * B, [ladder[b % len(ladder)] for b in range(B)]
+        for n in (1, 8):
+            g = torch.Generator().manual_seed(1000 * K + n)
+            x = (0.1 * torch.randn(B, 1, n * hop, generator=g)).to(dev)
+            frames = [n] * B
+            for graphs in (False, True):
+                enc, dec = StreamEncoder(m, B, graphs=graphs, n_q=K), StreamDecoder(m, B, K, graphs=graphs)
+                enc_c, dec_c = StreamEncoder(m, B, graphs=graphs, n_q=K), StreamDecoder(m, B, K, graphs=graphs)
+                mf = [enc.min_first_frames] * B
+                first = (0.1 * torch.randn(B, 1, mf[0] * hop, generator=g)).to(dev)
+                dec.decode_slots(enc.encode_slots(first, mf, n_q=full), mf, n_q=full)
+                dec_c.decode_slots(enc_c.encode_slots(first, mf), mf)
+                codes = enc_c.encode_slots(x, frames)
+                fns = {'a_encode': lambda: enc.encode_slots(x, frames, n_q=full),
+                       'b_encode': lambda: enc.encode_slots(x, frames, n_q=mixed),
+                       'c_encode': lambda: enc_c.encode_slots(x, frames),
+                       'a_decode': lambda: dec.decode_slots(codes, frames, n_q=full),
+                       'b_decode': lambda: dec.decode_slots(codes, frames, n_q=mixed),
+                       'c_decode': lambda: dec_c.decode_slots(codes, frames)}
+                if not graphs:  # the quantizer alone on the step's [B, 128, n] latent, launched back to back
+                    from encx import ops
+                    lat = torch.randn(B, 128, n, generator=g).to(dev)
+                    slots = torch.tensor([(n, 0)] * B, dtype=torch.int32, device=dev)
+                    nqt = torch.tensor(full, dtype=torch.int32, device=dev)
+                    cq = codes.permute(1, 0, 2).contiguous()
+                    fns.update({'q_fused_encode': lambda: ops.stream_rvq_encode_slots(lat, enc._books, slots, nqt),
+                                'q_layers_encode': lambda: ops.rvq_encode(lat, enc._embeds),
+                                'q_fused_decode': lambda: ops.stream_rvq_decode_slots(codes, enc._books, slots, nqt),
+                                'q_layers_decode': lambda: ops.rvq_decode(cq, enc._embeds)})
+                iters = {}
+                for k, fn in fns.items():
+                    for _ in range(5):
+                        fn()
+                    torch.cuda.synchronize()
+                    iters[k] = max(5, int(args.min_seconds * 1e3 / args.rounds / max(timed(fn, 5), 1e-3)) + 1)
+                ms = {k: [] for k in fns}
+                for _ in range(args.rounds):
+                    for k, fn in fns.items():
+                        ms[k].append(timed(fn, iters[k]))
+                row = {'K_max': K, 'n': n, 'mode': 'graph' if graphs else 'eager'}
+                row.update({k: stats(v) for k, v in ms.items()})
+                for side in ('encode', 'decode'):
+                    row[f'a_over_c_{side}'] = round(row[f'a_{side}']['ms'] / row[f'c_{side}']['ms'], 4)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+    return {'metric': f'ms per streaming step at B = {B}: a = n_q K_max per slot (fused quantizer), b = slots '
+                      'cycling 2, 4, .., K_max, c = the step without n_q at K_max (per-layer quantizer kernels)',
+            'device': torch.cuda.get_device_name(0), 'model': 'causal 24 kHz SEANet, random weights',
+            'rounds': args.rounds,
+            'timing': f'device events around blocks of steps, >= {args.min_seconds} s per case, the cases '
+                      'alternating round by round, after warm-up', 'rows': rows}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--nq', action='store_true', help='only the per-slot bandwidth section (B = 64)')
+    ap.add_argument('--nq-out', type=str, default=os.path.join(ROOT, 'profiles', 'stream', 'stream_bench_nq.json'))
     ap.add_argument('--slots', action='store_true', help='only the per-slot section (B = 64)')
     ap.add_argument('--slots-out', type=str,
                     default=os.path.join(ROOT, 'profiles', 'stream', 'stream_bench_slots.json'))
@@ -135,6 +207,15 @@ def main():
         torch.cuda.synchronize()
         iters = max(5, int(args.min_seconds * 1e3 / args.rounds / max(timed(fn, 5), 1e-3)) + 1)
         return stats([timed(fn, iters) for _ in range(args.rounds)]), iters
+
+    if args.nq:
+        with torch.no_grad():
+            res = nq_section(args, torch, m, dev, hop, timed)
+        if args.nq_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.nq_out)), exist_ok=True)
+            with open(args.nq_out, 'w') as f:
+                f.write(json.dumps(res, indent=1) + '\n')
+        return
 
     if args.slots:
         with torch.no_grad():
