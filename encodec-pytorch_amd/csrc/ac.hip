@@ -21,6 +21,10 @@
 // * encx_ac_encode_slots / encx_ac_decode_slots: the same two coders for the packets of a
 //   streaming step (encx.h): one flushed run per delivering slot, the count from the device slot
 //   table; the decoder starts a new run at step 0 of a slot's packet.
+// * encx_ac_encode_slots_nq / encx_ac_decode_slots_nq: the same for packet format 2 (encx.h): nq[b]
+//   symbols a frame from a second device table, the run ended by the short flush (the value in
+//   [low, high] with the most trailing zero bits, trailing zero bytes dropped), the decoder
+//   reading zero bits past the end of a payload. Both coders are the templates of the ones above.
 #include "common.h"
 
 // No mul+add contraction anywhere in this file: the same quantity computed by two kernels (e.g.
@@ -61,16 +65,16 @@ ENCX_DEV float block_max(float v, float* red) {
     return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
-// One row per workgroup: row r = n*K + k of a [N][K][card] problem (n = b*T + t).
+// One row per workgroup: row r = n*K + k of a [N][K][card] problem (n = b*T + t). The row's whole
+// arithmetic, shared by the kernel of every row and the one that skips rows by the slot tables.
 template <bool LOGITS>
-__global__ __launch_bounds__(CDF_THREADS) void softmax_cdf_kernel(
-    const float* __restrict__ in, int64_t ld_in, int card, float* __restrict__ probas,
+ENCX_DEV void softmax_cdf_row(
+    const int64_t row, const float* __restrict__ in, int64_t ld_in, int card, float* __restrict__ probas,
     int32_t* __restrict__ cdf, float roundoff, float qscale, int min_range, int64_t total_range,
     const int64_t* __restrict__ sym, int64_t s_b, int64_t s_k, int64_t s_t, int K, int T,
     int32_t* __restrict__ lohi, int* __restrict__ err) {
     __shared__ float redf[4];
     __shared__ int redi[4];
-    const int64_t row = blockIdx.x;
     const int tid = threadIdx.x;
     const float* x = in + row * ld_in;
     float mx = 0.f, sum = 1.f;
@@ -116,6 +120,38 @@ __global__ __launch_bounds__(CDF_THREADS) void softmax_cdf_kernel(
     if (tid == 0 && err && (int64_t)carry > total_range) atomicOr(err, 1);
 }
 
+template <bool LOGITS>
+__global__ __launch_bounds__(CDF_THREADS) void softmax_cdf_kernel(
+    const float* __restrict__ in, int64_t ld_in, int card, float* __restrict__ probas,
+    int32_t* __restrict__ cdf, float roundoff, float qscale, int min_range, int64_t total_range,
+    const int64_t* __restrict__ sym, int64_t s_b, int64_t s_k, int64_t s_t, int K, int T,
+    int32_t* __restrict__ lohi, int* __restrict__ err) {
+    softmax_cdf_row<LOGITS>(blockIdx.x, in, ld_in, card, probas, cdf, roundoff, qscale, min_range, total_range, sym,
+                            s_b, s_k, s_t, K, T, lohi, err);
+}
+
+// The rows of a slots step with a codebook count per slot (encx_lm_heads_slots): row (b, t, k) is
+// computed when step t + *dstep of slot b is live and k < nq[b]; a workgroup of any other row
+// leaves before it reads or writes anything (block-uniform).
+__global__ __launch_bounds__(CDF_THREADS) void softmax_cdf_slots_kernel(
+    const float* __restrict__ in, int64_t ld_in, int card, float* __restrict__ probas,
+    int32_t* __restrict__ cdf, float roundoff, float qscale, int min_range, int64_t total_range,
+    const int64_t* __restrict__ sym, int64_t s_b, int64_t s_k, int64_t s_t, int K, int T,
+    int32_t* __restrict__ lohi, int* __restrict__ err, const int32_t* __restrict__ slots,
+    const int32_t* __restrict__ nq, const int64_t* __restrict__ dstep, int n_max) {
+    const int64_t row = blockIdx.x;
+    const int64_t n = row / K;
+    const int k = (int)(row - n * K);
+    const int b = (int)(n / T);
+    const int tt = (int)(n - (int64_t)b * T) + (dstep ? (int)*dstep : 0);
+    int frames = slots[2 * b], q = nq[b];
+    frames = frames < 0 ? 0 : (frames > n_max ? n_max : frames);
+    q = q < 0 ? 0 : (q > K ? K : q);
+    if (tt < 0 || tt >= frames || k >= q) return;
+    softmax_cdf_row<true>(row, in, ld_in, card, probas, cdf, roundoff, qscale, min_range, total_range, sym, s_b, s_k,
+                          s_t, K, T, lohi, err);
+}
+
 struct BitOut {
     uint8_t* o;
     int64_t cap, pos;
@@ -154,10 +190,27 @@ ENCX_DEV int hibit128(u128 x) {  // index of the highest set bit, -1 for 0
     return h ? 127 - __builtin_clzll(h) : (l ? 63 - __builtin_clzll(l) : -1);
 }
 
+// where interval i of a run stands in lohi: one after the other, or (a packet of kq codebooks out
+// of a step's kmax, encx_ac_encode_slots_nq) the first kq of every kmax
+struct IvDense {
+    ENCX_DEV int64_t operator()(int64_t i) const { return i; }
+};
+struct IvRows {
+    int kq, kmax;
+    ENCX_DEV int64_t operator()(int64_t i) const {
+        const int64_t t = i / kq;
+        return t * kmax + (i - t * kq);
+    }
+};
+
 // One coder run: push the n intervals of lh in order, flush, -> the error code of encx_ac_encode;
 // *size = the bytes of the run (those past cap are counted, not written).
-ENCX_DEV int ac_encode_run(const int32_t* __restrict__ lh, int64_t n, int bits, uint8_t* __restrict__ out,
-                           int64_t cap, int64_t* size) {
+// SHORT (packet format 2, encx.h): the flush appends v = ceil(low / 2^j) 2^j for the largest j
+// with v <= high instead of low itself (j = 0), and the run's trailing zero bytes are dropped;
+// the decoder reads zero bits past the end, so it sees the same value in [low, high].
+template <bool SHORT, class IV>
+ENCX_DEV int ac_encode_run(const int32_t* __restrict__ lh, int64_t n, const IV at, int bits,
+                           uint8_t* __restrict__ out, int64_t cap, int64_t* size) {
     BitOut bo{out, cap, 0, 0ull, 0};
     const uint64_t R = 1ull << bits;
     u128 low = 0, high = 0;
@@ -168,8 +221,8 @@ ENCX_DEV int ac_encode_run(const int32_t* __restrict__ lh, int64_t n, int bits, 
         uint32_t iv[16];
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
-            const int64_t q = 2 * i0 + u;
-            iv[u] = (uint32_t)lh[q < 2 * n ? q : 2 * n - 1];
+            const int64_t i = i0 + (u >> 1);
+            iv[u] = (uint32_t)lh[2 * at(i < n ? i : n - 1) + (u & 1)];
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -201,12 +254,23 @@ ENCX_DEV int ac_encode_run(const int32_t* __restrict__ lh, int64_t n, int bits, 
         }
     }
     if (!e) {
-        bo.put_msb_first((uint64_t)low, max_bit + 1);  // flush (ac.py:160-167); max_bit <= 61
+        uint64_t v = (uint64_t)low;  // flush (ac.py:160-167); max_bit <= 61, so low <= high < 2^62
+        if (SHORT) {
+            // rounding up to a multiple of 2^j is monotone in j: climb while the value stays <= high
+            for (int j = 1; j <= max_bit + 1; ++j) {
+                const uint64_t r = ((v >> j) + ((v & lowmask(j)) != 0)) << j;
+                if (r > (uint64_t)high) break;
+                v = r;
+            }
+        }
+        bo.put_msb_first(v, max_bit + 1);
         if (bo.nb) {
             if (bo.pos < cap) bo.o[bo.pos] = (uint8_t)(bo.acc & 0xff);
             ++bo.pos;
         }
         if (bo.pos > cap) e = 2;
+        if (SHORT && !e)
+            while (bo.pos > 0 && bo.o[bo.pos - 1] == 0) --bo.pos;
     }
     *size = bo.pos;
     return e;
@@ -218,7 +282,7 @@ __global__ void ac_encode_kernel(const int32_t* __restrict__ lohi, int64_t n, in
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= S) return;
     int64_t size;
-    err[s] = ac_encode_run(lohi + (int64_t)s * n * 2, n, bits, out + (int64_t)s * cap, cap, &size);
+    err[s] = ac_encode_run<false>(lohi + (int64_t)s * n * 2, n, IvDense{}, bits, out + (int64_t)s * cap, cap, &size);
     nbytes[s] = size;
 }
 
@@ -240,18 +304,49 @@ __global__ void ac_encode_slots_kernel(const int32_t* __restrict__ lohi, int B, 
     uint8_t* o = out + (int64_t)b * stride;
     o[0] = (uint8_t)frames;
     int64_t size;
-    err[b] = ac_encode_run(lohi + (int64_t)b * n_max * K * 2, (int64_t)frames * K, bits, o + 1, stride - 1, &size);
+    err[b] = ac_encode_run<false>(lohi + (int64_t)b * n_max * K * 2, (int64_t)frames * K, IvDense{}, bits, o + 1,
+                                  stride - 1, &size);
     nbytes[b] = 1 + size;
+}
+
+// The packet of format 2 (encx.h): slot b pushes the first nq[b] intervals of each of its first
+// `frames` rows of lohi [B][n_max][K][2], ends with the short flush and writes [frames | nq[b] |
+// payload]. Rows k >= nq[b] and frames past the count are never addressed.
+__global__ void ac_encode_slots_nq_kernel(const int32_t* __restrict__ lohi, int B, int n_max, int K,
+                                          const int32_t* __restrict__ slots, const int32_t* __restrict__ nq, int bits,
+                                          uint8_t* __restrict__ out, int64_t stride, int64_t* __restrict__ nbytes,
+                                          int* __restrict__ err) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int frames = slots[2 * b], q = nq[b];
+    frames = frames < 0 ? 0 : (frames > n_max ? n_max : frames);
+    q = q < 0 ? 0 : (q > K ? K : q);
+    if (!frames || !q) {
+        nbytes[b] = 0;
+        err[b] = 0;
+        return;
+    }
+    uint8_t* o = out + (int64_t)b * stride;
+    o[0] = (uint8_t)frames;
+    o[1] = (uint8_t)q;
+    int64_t size;
+    err[b] = ac_encode_run<true>(lohi + (int64_t)b * n_max * K * 2, (int64_t)frames * q, IvRows{q, K}, bits, o + 2,
+                                 stride - 2, &size);
+    nbytes[b] = 2 + size;
 }
 
 // decoder state per stream (ENCX_AC_STATE int64 words): low, high, current (128 bits each,
 // low word first), max_bit, bits consumed
-__global__ __launch_bounds__(64) void ac_decode_kernel(
+// NQ (encx_ac_decode_slots_nq, packet format 2): the slot pulls its first nq[s] of the K codebooks
+// (cdf row k of the slot still at (s K + k) card), bits past the end of the payload read as 0
+// (the short flush dropped them), and codes / next_idx of the codebooks it does not carry are 0.
+template <bool NQ>
+ENCX_DEV void ac_decode_step(
     const uint8_t* __restrict__ data, int64_t stride, const int64_t* __restrict__ nbytes,
     int64_t* __restrict__ state, const int32_t* __restrict__ cdf, int K, int card, int bits,
     int64_t* __restrict__ codes, int64_t c_s, int64_t c_k, int64_t c_t, int64_t t,
     const int64_t* __restrict__ dstep, int64_t* __restrict__ next_idx, int* __restrict__ err,
-    const int32_t* __restrict__ slots, int n_max) {
+    const int32_t* __restrict__ slots, int n_max, const int32_t* __restrict__ nq) {
     const int s = blockIdx.x, lane = threadIdx.x;
     if (err[s]) return;  // the stream already failed; later steps leave it as it is
     if (dstep) t += *dstep;
@@ -269,25 +364,32 @@ __global__ __launch_bounds__(64) void ac_decode_kernel(
             pos = 0;
         }
     }
-    const int64_t nbits = nbytes[s] * 8;
+    int Kq = K;
+    if (NQ) {
+        Kq = nq[s];
+        Kq = Kq < 0 ? 0 : (Kq > K ? K : Kq);
+    }
+    const int64_t nbits = (NQ && nbytes[s] < 0 ? 0 : nbytes[s]) * 8;
     const uint8_t* src = data + (int64_t)s * stride;
     const uint64_t R = 1ull << bits;
     int e = 0;
-    for (int k = 0; k < K; ++k) {
+    for (int k = 0; k < Kq; ++k) {
         // the reference decoder has no bound on max_bit (ac.py:217-260); a stream its encoder
         // wrote keeps it <= 61 after every pull, so past 96 the stream is not one it could write
         if (max_bit > 96) { e = 3; break; }
         uint64_t delta = (uint64_t)(high - low) + 1;
         if (delta < R) {  // ac.py:226-233
             const int sh = bits - (63 - __builtin_clzll(delta));
-            if (pos + sh > nbits) { e = 1; break; }  // BitUnpacker ran dry: pull returns None
+            if (!NQ && pos + sh > nbits) { e = 1; break; }  // BitUnpacker ran dry: pull returns None
             // the sh (<= 31) stream bits from `pos` span at most 5 bytes: load them together
             const int64_t b0 = pos >> 3, last = (nbits >> 3) - 1;
             uint64_t win = 0;
 #pragma unroll
             for (int u = 0; u < 5; ++u) {
                 const int64_t bi = b0 + u <= last ? b0 + u : last;
-                win |= (uint64_t)src[bi] << (8 * u);
+                uint64_t byte = src[NQ && bi < 0 ? 0 : bi];
+                if (NQ && b0 + u > last) byte = 0;  // past the end of the payload
+                win |= byte << (8 * u);
             }
             const uint64_t chunk = (win >> (pos & 7)) & lowmask(sh);   // stream bit pos at bit 0
             cur = (cur << sh) | (u128)(__builtin_bitreverse64(chunk) >> (64 - sh));
@@ -340,6 +442,11 @@ __global__ __launch_bounds__(64) void ac_decode_kernel(
             if (next_idx) next_idx[(int64_t)s * K + k] = sym + 1;
         }
     }
+    if (NQ && lane == 0 && !e)
+        for (int k = Kq; k < K; ++k) {
+            if (codes) codes[s * c_s + k * c_k + t * c_t] = 0;
+            if (next_idx) next_idx[(int64_t)s * K + k] = 0;
+        }
     if (lane == 0) {
         const u128 w[3] = {low, high, cur};
 #pragma unroll
@@ -351,6 +458,26 @@ __global__ __launch_bounds__(64) void ac_decode_kernel(
         stt[7] = pos;
         err[s] = e;
     }
+}
+
+__global__ __launch_bounds__(64) void ac_decode_kernel(
+    const uint8_t* __restrict__ data, int64_t stride, const int64_t* __restrict__ nbytes,
+    int64_t* __restrict__ state, const int32_t* __restrict__ cdf, int K, int card, int bits,
+    int64_t* __restrict__ codes, int64_t c_s, int64_t c_k, int64_t c_t, int64_t t,
+    const int64_t* __restrict__ dstep, int64_t* __restrict__ next_idx, int* __restrict__ err,
+    const int32_t* __restrict__ slots, int n_max) {
+    ac_decode_step<false>(data, stride, nbytes, state, cdf, K, card, bits, codes, c_s, c_k, c_t, t, dstep, next_idx,
+                          err, slots, n_max, nullptr);
+}
+
+__global__ __launch_bounds__(64) void ac_decode_nq_kernel(
+    const uint8_t* __restrict__ data, int64_t stride, const int64_t* __restrict__ nbytes,
+    int64_t* __restrict__ state, const int32_t* __restrict__ cdf, int K, int card, int bits,
+    int64_t* __restrict__ codes, int64_t c_s, int64_t c_k, int64_t c_t, const int64_t* __restrict__ dstep,
+    int64_t* __restrict__ prev, int* __restrict__ err, const int32_t* __restrict__ slots, int n_max,
+    const int32_t* __restrict__ nq) {
+    ac_decode_step<true>(data, stride, nbytes, state, cdf, K, card, bits, codes, c_s, c_k, c_t, (int64_t)0, dstep,
+                         prev, err, slots, n_max, nq);
 }
 
 __global__ void ac_lohi_kernel(const int32_t* __restrict__ cdf, int64_t ld, const int64_t* __restrict__ sym,
@@ -391,6 +518,25 @@ int encx_lm_softmax_cdf_launch(const float* in, int64_t rows, int card, int64_t 
         hipLaunchKernelGGL(softmax_cdf_kernel<false>, dim3((unsigned)rows), dim3(CDF_THREADS), 0, st, in, ld_in,
                            card, probas, cdf, roundoff, qscale, min_range, (int64_t)1 << total_range_bits,
                            sym, s_b, s_k, s_t, K, T, lohi, err);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
+
+// shared with lm.hip (encx_lm_heads_slots): the logits rows of a slots step, skipped by the tables
+int encx_lm_softmax_cdf_slots_launch(const float* in, int64_t rows, int card, float* probas, int32_t* cdf,
+                                     int total_range_bits, float roundoff, int min_range, const int64_t* sym,
+                                     int64_t s_b, int64_t s_k, int64_t s_t, int K, int T, int32_t* lohi, int* err,
+                                     const int32_t* slots, const int32_t* nq, const int64_t* dstep, int n_max,
+                                     hipStream_t st) {
+    ENCX_REQUIRE(total_range_bits >= 1 && total_range_bits <= 30 && min_range >= 2 && card >= 1);
+    const double total = (double)(1ll << total_range_bits);
+    const double alpha = (double)min_range * card / total;  // ac.py:42-43
+    ENCX_REQUIRE(alpha <= 1.0);
+    const float qscale = (float)((1.0 - alpha) * total);
+    ENCX_REQUIRE(in && slots && nq && rows >= 1 && rows <= INT32_MAX && T >= 1 && K >= 1 && (!sym || lohi));
+    hipLaunchKernelGGL(softmax_cdf_slots_kernel, dim3((unsigned)rows), dim3(CDF_THREADS), 0, st, in, (int64_t)card,
+                       card, probas, cdf, roundoff, qscale, min_range, (int64_t)1 << total_range_bits, sym, s_b, s_k,
+                       s_t, K, T, lohi, err, slots, nq, dstep, n_max);
     ENCX_CHECK_LAUNCH();
     return 0;
 }
@@ -469,6 +615,32 @@ int encx_ac_decode_slots(const uint8_t* data, int64_t stride, const int64_t* nby
     hipLaunchKernelGGL(ac_decode_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, data, stride, nbytes,
                        state, cdf, (int)K, (int)card, total_range_bits, codes, c_s, c_k, c_t, (int64_t)0, dev_step,
                        prev, err, slots, (int)n_max);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
+
+int encx_ac_encode_slots_nq(const int32_t* lohi, int64_t B, int64_t n_max, int64_t K, const int32_t* slots,
+                            const int32_t* nq, int total_range_bits, uint8_t* out, int64_t out_stride,
+                            int64_t* nbytes, int* err, encx_stream_t stream) {
+    ENCX_REQUIRE(lohi && slots && nq && out && nbytes && err);
+    ENCX_REQUIRE(B >= 1 && B <= 64 && K >= 1 && K <= 64 && n_max >= 1 && n_max <= 255);
+    ENCX_REQUIRE(total_range_bits >= 1 && total_range_bits <= 30 && out_stride >= 2);
+    hipLaunchKernelGGL(ac_encode_slots_nq_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, lohi, (int)B, (int)n_max,
+                       (int)K, slots, nq, total_range_bits, out, out_stride, nbytes, err);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
+
+int encx_ac_decode_slots_nq(const uint8_t* data, int64_t stride, const int64_t* nbytes, int64_t B, int64_t* state,
+                            const int32_t* cdf, int64_t K, int64_t card, int total_range_bits, int64_t* codes,
+                            int64_t c_s, int64_t c_k, int64_t c_t, int64_t n_max, const int64_t* dev_step,
+                            const int32_t* slots, const int32_t* nq, int64_t* prev, int* err, encx_stream_t stream) {
+    ENCX_REQUIRE(data && nbytes && state && cdf && codes && dev_step && slots && nq && prev && err);
+    ENCX_REQUIRE(B >= 1 && B <= 64 && K >= 1 && K <= 64 && n_max >= 1 && n_max <= 255 && stride >= 1);
+    ENCX_REQUIRE(card >= 1 && card <= INT32_MAX && total_range_bits >= 1 && total_range_bits <= 30);
+    hipLaunchKernelGGL(ac_decode_nq_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, data, stride, nbytes,
+                       state, cdf, (int)K, (int)card, total_range_bits, codes, c_s, c_k, c_t, dev_step, prev, err,
+                       slots, (int)n_max, nq);
     ENCX_CHECK_LAUNCH();
     return 0;
 }

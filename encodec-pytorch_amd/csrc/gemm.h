@@ -30,6 +30,14 @@ struct ld_vec { static constexpr bool value = false; };
 template <class LD>
 struct ld_vec<LD, decltype((void)LD::VEC)> { static constexpr bool value = LD::VEC; };
 
+// epilogues that can tell that nobody wants a tile declare `static constexpr bool SKIP = true` and
+// bool skip(m0, m1, n0, n1) over the tile's rows [m0, m1) and columns [n0, n1) (block-uniform): such
+// a workgroup leaves before it loads an operand or issues an MFMA
+template <class EP, class = void>
+struct ep_skip { static constexpr bool value = false; };
+template <class EP>
+struct ep_skip<EP, decltype((void)EP::SKIP)> { static constexpr bool value = EP::SKIP; };
+
 template <int BM, int BN, int WM, int WN, int BK, class LD, class EP>
 __global__ __launch_bounds__(256) void gemm_kernel(LD ld, EP ep, int M, int N, int Kred, int kchunk) {
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
@@ -38,6 +46,9 @@ __global__ __launch_bounds__(256) void gemm_kernel(LD ld, EP ep, int M, int N, i
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm0 = (wave / WN) * TM * 32, wn0 = (wave % WN) * TN * 32;
     const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+    if constexpr (ep_skip<EP>::value) {
+        if (ep.skip(m0, min(M, m0 + BM), n0, min(N, n0 + BN))) return;
+    }
     const int kbeg = blockIdx.z * kchunk, kend = min(Kred, kbeg + kchunk);
     const int h = lane >> 5, l32 = lane & 31;
     f32x16 acc[TM][TN];

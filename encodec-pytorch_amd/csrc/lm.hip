@@ -124,6 +124,33 @@ struct EpBias {
     }
 };
 
+// The heads of a slots step with a codebook count per slot (encx_lm_heads_slots): logits = acc +
+// bias as EpBias, and a tile is skipped (gemm.h ep_skip) when none of its rows is a live row of a
+// slot that uses one of its codebooks. Rows of a slot are adjacent and its live rows come first,
+// so per slot the tile's lowest row decides; column n belongs to codebook n / card, so the tile's
+// lowest codebook decides (a tile that straddles two codebooks is computed if either is wanted).
+struct EpHeadsSlots {
+    static constexpr bool SKIP = true;
+    const float* bias;
+    float* out;
+    int ldo, T, K, card, n_max;
+    const int32_t* slots;
+    const int32_t* nq;
+    const int64_t* dstep;  // nullable
+    ENCX_DEV bool skip(int m0, int m1, int n0, int n1) const {
+        const int k0 = n0 / card, d = dstep ? (int)*dstep : 0;
+        const int b0 = m0 / T, b1 = (m1 - 1) / T;
+        for (int b = b0; b <= b1; ++b) {
+            int frames = slots[2 * b];
+            frames = frames > n_max ? n_max : frames;
+            const int tt = (b == b0 ? m0 - b * T : 0) + d;
+            if (nq[b] > k0 && tt >= 0 && tt < frames) return false;
+        }
+        return true;
+    }
+    ENCX_DEV void operator()(int m, int n, float v) const { out[(int64_t)m * ldo + n] = v + bias[n]; }
+};
+
 constexpr int LN_MAXV = 8;  // D <= 64 * 8
 
 // LayerNorm over one row held by one wave (lane i owns d = i, i + 64, ...), eps 1e-5, biased
@@ -215,6 +242,55 @@ __global__ void lm_slots_advance_kernel(const int32_t* __restrict__ slots, int B
     frames = frames < 0 ? 0 : (frames > n_max ? n_max : frames);
     if (!frames) return;
     if (codes) {
+        int64_t c = codes[b * s_b + k * s_k + (int64_t)(frames - 1) * s_t] + 1;
+        prev[i] = c < 0 ? 0 : (c >= card1 ? card1 - 1 : c);
+    }
+    if (k == 0) pos[b] = (slots[2 * b + 1] ? 0 : pos[b]) + frames;
+}
+
+// lm_input_slots_kernel with nq[b] codebooks in the row (encx.h: the LM with a K per slot and
+// step): the sum runs over k < nq[b], prev[b][k] is 0 where the slot's last frame lacked k (the
+// kernels that end a packet see to it), and rows k >= nq[b] of codes are never addressed.
+__global__ __launch_bounds__(64) void lm_input_slots_nq_kernel(const int64_t* __restrict__ codes, int64_t s_b,
+                                                               int64_t s_k, int64_t s_t, int K, int T, SlotRows sr,
+                                                               const int32_t* __restrict__ nq,
+                                                               const int64_t* __restrict__ prev,
+                                                               const float* __restrict__ emb, int64_t card1, int D,
+                                                               const float* ln_w, const float* ln_b, float max_period,
+                                                               float* __restrict__ x) {
+    const int row = blockIdx.x, lane = threadIdx.x;
+    const int b = row / T, t = row - b * T;
+    int tt;
+    bool live, first;
+    int64_t s;
+    sr.at(b, t, tt, live, first, s);
+    int q = nq[b];
+    q = q < 0 ? 0 : (q > K ? K : q);
+    int64_t my = 0;
+    if (lane < q && live) {
+        if (codes && tt > 0) my = codes[b * s_b + lane * s_k + (int64_t)(tt - 1) * s_t] + 1;
+        else my = (first && tt == 0) ? 0 : prev[(int64_t)b * K + lane];
+        my = my < 0 ? 0 : (my >= card1 ? card1 - 1 : my);
+    }
+    lm_input_row(my, lane, q, emb, card1, D, ln_w, ln_b, (float)(s - 1), max_period, x + (int64_t)row * D);
+}
+
+// lm_slots_advance_kernel with nq[b]: prev[b][k] = 0 for k >= nq[b] (the next frame sees the start
+// index where this packet's last frame had no codebook k), with or without codes
+__global__ void lm_slots_advance_nq_kernel(const int32_t* __restrict__ slots, const int32_t* __restrict__ nq, int B,
+                                           int K, int n_max, int64_t* __restrict__ pos, int64_t* __restrict__ prev,
+                                           const int64_t* __restrict__ codes, int64_t s_b, int64_t s_k, int64_t s_t,
+                                           int64_t card1) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * K) return;
+    const int b = i / K, k = i - b * K;
+    int frames = slots[2 * b], q = nq[b];
+    frames = frames < 0 ? 0 : (frames > n_max ? n_max : frames);
+    q = q < 0 ? 0 : (q > K ? K : q);
+    if (!frames) return;
+    if (k >= q) {
+        prev[i] = 0;
+    } else if (codes) {
         int64_t c = codes[b * s_b + k * s_k + (int64_t)(frames - 1) * s_t] + 1;
         prev[i] = c < 0 ? 0 : (c >= card1 ? card1 - 1 : c);
     }
@@ -463,6 +539,9 @@ __global__ __launch_bounds__(256) void lm_gemv_kernel(const float* __restrict__ 
     const int tid = threadIdx.x;
     const int nl = tid % GV_NB, r = tid / GV_NB;
     const int n0 = blockIdx.x * GV_NB, m0 = blockIdx.y * GV_MB;
+    if constexpr (ep_skip<EP>::value) {  // gemm.h: a tile nobody wants
+        if (ep.skip(m0, min(M, m0 + GV_MB), n0, min(N, n0 + GV_NB))) return;
+    }
     // staging roles: x -> thread tid loads 4 consecutive k of row tid / 32; w -> 4 float4 of
     // rows (tid / 32) + 8 i, i < 4, at k offset 4 * (tid % 32)
     const int sr = tid / 32, sk = 4 * (tid % 32);
@@ -541,6 +620,11 @@ int encx_lm_softmax_cdf_launch(const float* logits, int64_t rows, int card, int6
                                float roundoff, int min_range, const int64_t* sym, int64_t s_b,
                                int64_t s_k, int64_t s_t, int K, int T, int32_t* lohi, int* err,
                                hipStream_t st);
+int encx_lm_softmax_cdf_slots_launch(const float* in, int64_t rows, int card, float* probas, int32_t* cdf,
+                                     int total_range_bits, float roundoff, int min_range, const int64_t* sym,
+                                     int64_t s_b, int64_t s_k, int64_t s_t, int K, int T, int32_t* lohi, int* err,
+                                     const int32_t* slots, const int32_t* nq, const int64_t* dstep, int n_max,
+                                     hipStream_t st);
 
 extern "C" {
 
@@ -709,6 +793,57 @@ int encx_lm_slots_advance(const int32_t* slots, int64_t B, int64_t K, int64_t n_
                        slots, (int)B, (int)K, (int)n_max, pos, prev, codes, s_b, s_k, s_t, card1);
     ENCX_CHECK_LAUNCH();
     return 0;
+}
+
+int encx_lm_input_slots_nq(const int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t, int64_t B, int64_t K,
+                           int64_t T, int64_t n_max, const int32_t* slots, const int32_t* nq, const int64_t* pos,
+                           const int64_t* prev, const int64_t* dev_step, const float* emb, int64_t card1, int64_t D,
+                           const float* ln_w, const float* ln_b, float max_period, float* x, encx_stream_t stream) {
+    ENCX_REQUIRE(slots && nq && pos && prev && emb && ln_w && ln_b && x);
+    ENCX_REQUIRE(B >= 1 && B <= 64 && K >= 1 && K <= 64 && n_max >= 1 && n_max <= 255 && T >= 1 && T <= n_max);
+    ENCX_REQUIRE(D >= 4 && D % 2 == 0 && D <= 64 * LN_MAXV && card1 >= 1);
+    hipLaunchKernelGGL(lm_input_slots_nq_kernel, dim3((unsigned)(B * T)), dim3(64), 0, (hipStream_t)stream, codes,
+                       s_b, s_k, s_t, (int)K, (int)T, SlotRows{slots, pos, dev_step, (int)n_max, 0}, nq, prev, emb,
+                       card1, (int)D, ln_w, ln_b, max_period, x);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
+
+int encx_lm_slots_advance_nq(const int32_t* slots, const int32_t* nq, int64_t B, int64_t K, int64_t n_max,
+                             int64_t* pos, int64_t* prev, const int64_t* codes, int64_t s_b, int64_t s_k,
+                             int64_t s_t, int64_t card1, encx_stream_t stream) {
+    ENCX_REQUIRE(slots && nq && pos && prev);
+    ENCX_REQUIRE(B >= 1 && B <= 64 && K >= 1 && K <= 64 && n_max >= 1 && n_max <= 255 && card1 >= 1);
+    hipLaunchKernelGGL(lm_slots_advance_nq_kernel, dim3((unsigned)cdiv(B * K, 256)), dim3(256), 0,
+                       (hipStream_t)stream, slots, nq, (int)B, (int)K, (int)n_max, pos, prev, codes, s_b, s_k, s_t,
+                       card1);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
+
+int encx_lm_heads_slots(const float* x, int64_t B, int64_t T, int64_t n_max, int64_t D, const float* w,
+                        const float* bias, int64_t K, int64_t card, const int32_t* slots, const int32_t* nq,
+                        const int64_t* dev_step, float* work, float* probas, int32_t* cdf, int total_range_bits,
+                        float roundoff, int min_range, const int64_t* sym, int64_t s_b, int64_t s_k, int64_t s_t,
+                        int32_t* lohi, int* err, encx_stream_t stream) {
+    ENCX_REQUIRE(x && w && bias && slots && nq && work && (probas || cdf));
+    ENCX_REQUIRE(B >= 1 && B <= 64 && K >= 1 && K <= 64 && n_max >= 1 && n_max <= 255 && T >= 1 && T <= n_max);
+    ENCX_REQUIRE(D >= 1 && card >= 1 && card <= 65536 && (!sym || (cdf && lohi)));
+    // what the cdf stage would refuse, before the GEMM is launched (ac.py:42-43: alpha <= 1)
+    ENCX_REQUIRE(total_range_bits >= 1 && total_range_bits <= 30 && min_range >= 2);
+    ENCX_REQUIRE((double)min_range * (double)card <= (double)(1ll << total_range_bits));
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t N = B * T;
+    ENCX_REQUIRE(N * K * card <= INT32_MAX);
+    // the K per-codebook projections as one GEMM (encx_lm_heads), whole tiles skipped by the tables
+    int rc = lm_linear(x, (int)D, w, (int)D, (int)N, (int)(K * card), (int)D,
+                       EpHeadsSlots{bias, work, (int)(K * card), (int)T, (int)K, (int)card, (int)n_max, slots, nq,
+                                    dev_step},
+                       st);
+    if (rc) return rc;
+    return encx_lm_softmax_cdf_slots_launch(work, N * K, (int)card, probas, cdf, total_range_bits, roundoff,
+                                            min_range, sym, s_b, s_k, s_t, (int)K, (int)T, lohi, err, slots, nq,
+                                            dev_step, (int)n_max, st);
 }
 
 namespace {

@@ -17,7 +17,11 @@ same cdfs bit for bit.
 `LMStreamEncoder` / `LMStreamDecoder` are the same coder for live streams (the slots of
 encx/streaming.py): one flushed coder run per slot and step, the LM's position, last codes and
 key/value ring carried per slot on the device, so a stream has no length limit and a captured
-step replays whatever the slots deliver.
+step replays whatever the slots deliver. With lm_format=2 every slot and step has its own
+codebook count n_q[b] <= K (packet format 2 of include/encx.h: the LM row sums the embeddings of
+the codebooks the packet carries, a codebook the previous frame lacked enters with the start
+index, and the coder run ends with the short flush); the counts are a second device table, so
+the same graphs serve any mix.
 
 `nll(codes)` trains the LM (csrc/lm_train.hip): the teacher-forced forward is the encoder's own
 pass, so the loss is the log-probability the arithmetic coder will see, and one autograd Function
@@ -492,7 +496,10 @@ class _LMSlots:
     arguments is a pure host check. A session is a snapshot of the LM's stacked heads and
     embeddings: build a new one after changing the LM's weights."""
 
-    def __init__(self, lm: 'LMModel', batch: int, K: int, max_frames: int, graphs: bool):
+    def __init__(self, lm: 'LMModel', batch: int, K: int, max_frames: int, graphs: bool, lm_format: int = 1):
+        if lm_format not in (1, 2):
+            raise ValueError(f'encx LM streaming: lm_format {lm_format!r} (1: a fixed K, 2: n_q per slot and step)')
+        self.lm_format = int(lm_format)
         if not 1 <= batch <= MAX_SLOTS:
             raise ValueError(f'encx LM streaming: batch {batch} (1..{MAX_SLOTS})')
         if not 1 <= K <= min(lm.n_q, 64):
@@ -506,6 +513,7 @@ class _LMSlots:
         self.failed: tp.Set[int] = set()
         self._ready = False
         self._tab = None  # the slot table as last uploaded
+        self._nq_tab = None  # lm_format 2: the nq table as last uploaded
         self._graphs: tp.Dict[int, tp.Any] = {}
 
     def reset(self):
@@ -531,6 +539,13 @@ class _LMSlots:
                 raise ValueError(f'encx LM streaming: slot {b} failed on a bad packet; restart([{b}]) it first')
         return frames, n_max
 
+    def _check_n_q(self, frames, n_q):
+        """n_q goes with lm_format=2 and only with it -> the nq table (streaming.check_n_q), or None."""
+        from .streaming import check_n_q
+        if (self.lm_format == 2) != (n_q is not None):
+            raise ValueError('encx LM streaming: n_q goes with lm_format=2, and only with it')
+        return check_n_q(frames, n_q, self.K) if n_q is not None else None
+
     def _ensure(self):
         if self._ready:
             return
@@ -544,6 +559,7 @@ class _LMSlots:
         self._pos = torch.zeros(B, dtype=torch.int64, device=dev)
         self._prev = torch.zeros(B, K, dtype=torch.int64, device=dev)
         self._slots = torch.zeros(B, 2, dtype=torch.int32, device=dev)
+        self._nq = torch.zeros(B, dtype=torch.int32, device=dev)
         self._cols = torch.arange(self.max_frames, device=dev, dtype=torch.int32)
         self._ready = True
 
@@ -553,6 +569,11 @@ class _LMSlots:
             self._slots.copy_(torch.tensor(tab, dtype=torch.int32))
             self._tab = tab
 
+    def _put_nq(self, n_q):
+        if n_q is not None and n_q != self._nq_tab:  # uploaded only when it changed
+            self._nq.copy_(torch.tensor(n_q, dtype=torch.int32))
+            self._nq_tab = list(n_q)
+
     def _rows(self, T, n_max, codes, dstep):
         """The LM input and every layer for T rows per slot under the slot table -> x [B*T][dim]."""
         lm, tr = self.lm, self.lm.transformer
@@ -561,10 +582,12 @@ class _LMSlots:
         cs = codes.stride() if codes is not None else (0, 0, 0)
         dptr = dstep.data_ptr() if dstep is not None else None
         x = torch.empty(B * T, D, device=self.dev)
-        call('encx_lm_input_slots', codes.data_ptr() if codes is not None else None, cs[0], cs[1], cs[2], B, K, T,
-             n_max, self._slots.data_ptr(), self._pos.data_ptr(), self._prev.data_ptr(), dptr, lm._emb.data_ptr(),
-             lm.card + 1, D, tr.norm_in.weight.data_ptr(), tr.norm_in.bias.data_ptr(), float(tr.max_period),
-             x.data_ptr(), st)
+        nq = (self._nq.data_ptr(),) if self.lm_format == 2 else ()
+        call('encx_lm_input_slots_nq' if nq else 'encx_lm_input_slots',
+             codes.data_ptr() if codes is not None else None, cs[0], cs[1], cs[2], B, K, T,
+             n_max, self._slots.data_ptr(), *nq, self._pos.data_ptr(), self._prev.data_ptr(), dptr,
+             lm._emb.data_ptr(), lm.card + 1, D, tr.norm_in.weight.data_ptr(), tr.norm_in.bias.data_ptr(),
+             float(tr.max_period), x.data_ptr(), st)
         work = torch.empty((int(lib.encx_lm_layer_workspace(B * T, D, Fh)) + 3) // 4, device=self.dev)
         for i, layer in enumerate(tr.layers):
             y = torch.empty_like(x)
@@ -576,17 +599,30 @@ class _LMSlots:
 
     def _advance(self, n_max, codes):
         cs = codes.stride() if codes is not None else (0, 0, 0)
-        call('encx_lm_slots_advance', self._slots.data_ptr(), self.B, self.K, n_max, self._pos.data_ptr(),
-             self._prev.data_ptr(), codes.data_ptr() if codes is not None else None, cs[0], cs[1], cs[2],
-             self.lm.card + 1, stream())
+        nq = (self._nq.data_ptr(),) if self.lm_format == 2 else ()
+        call('encx_lm_slots_advance_nq' if nq else 'encx_lm_slots_advance', self._slots.data_ptr(), *nq, self.B,
+             self.K, n_max, self._pos.data_ptr(), self._prev.data_ptr(),
+             codes.data_ptr() if codes is not None else None, cs[0], cs[1], cs[2], self.lm.card + 1, stream())
 
-    def _run(self, key, body, frames):
+    def _heads_nq(self, x, T, n_max, dstep, probas=None, cdf=None, sym=None, lohi=None, err=None):
+        """lm._heads for the live rows and the codebooks k < nq[b] of a slots step (lm_format 2)."""
+        lm = self.lm
+        work = torch.empty((int(lib.encx_lm_heads_workspace(self.B * T, self.K, lm.card)) + 3) // 4, device=self.dev)
+        s = sym.stride() if sym is not None else (0, 0, 0)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        call('encx_lm_heads_slots', x.data_ptr(), self.B, T, n_max, lm.dim, lm._lin_w.data_ptr(),
+             lm._lin_b.data_ptr(), self.K, lm.card, self._slots.data_ptr(), self._nq.data_ptr(), ptr(dstep),
+             work.data_ptr(), ptr(probas), ptr(cdf), TOTAL_RANGE_BITS, ROUNDOFF, MIN_RANGE, ptr(sym), s[0], s[1], s[2],
+             ptr(lohi), ptr(err), stream())
+
+    def _run(self, key, body, frames, n_q=None):
         """Fill this step's slot table; -> the graph of body(key) to replay, or None (run the body
         eagerly). The first step of a key runs the body once eagerly under an EMPTY table (every
         row dead: each kernel is loaded, no state moves), then captures it; the table is device
         memory, so the graph replays for any counts."""
         if not self.graphs:
             self._put_slots(frames)
+            self._put_nq(n_q)
             return None
         g = self._graphs.get(key)
         if g is None:
@@ -598,6 +634,7 @@ class _LMSlots:
                 body(key)
             self._graphs[key] = g
         self._put_slots(frames)
+        self._put_nq(n_q)
         return g
 
 
@@ -612,10 +649,18 @@ class LMStreamEncoder(_LMSlots):
     payloads[b] is the coded chunk of slot b (b'' for a slot with 0 frames); packets(...) returns
     the same with the header byte in front. Slot b's columns past frames[b] are not read. A slot's
     bytes are those of the same stream alone in a session of one. probas=True keeps the
-    probabilities of the last step's rows in last_probas [B, n_max, K, card]."""
+    probabilities of the last step's rows in last_probas [B, n_max, K, card].
 
-    def __init__(self, lm, batch: int, K: int, max_frames: int = 8, graphs: bool = True, probas: bool = False):
-        super().__init__(lm, batch, K, max_frames, graphs)
+    lm_format=2: K is the session's largest count and every step names the count of each slot,
+
+        payloads = enc.encode_slots(codes, frames, n_q)   # rows k >= n_q[b] of codes are not read
+
+    packets(...) then carries the two header bytes (n, n_q[b]) of packet format 2. The rows of
+    last_probas / last_cdf that a step skipped (dead frames, k >= n_q[b]) hold whatever they held."""
+
+    def __init__(self, lm, batch: int, K: int, max_frames: int = 8, graphs: bool = True, probas: bool = False,
+                 lm_format: int = 1):
+        super().__init__(lm, batch, K, max_frames, graphs, lm_format)
         self._want_probas = bool(probas)
         self._bufs: tp.Dict[int, tp.Any] = {}
         self.last_probas = self.last_cdf = None
@@ -624,7 +669,7 @@ class LMStreamEncoder(_LMSlots):
         b = self._bufs.get(n)
         if b is None:
             dev, B, K, card = self.dev, self.B, self.K, self.lm.card
-            stride = 1 + int(lib.encx_ac_encode_capacity(n * K, TOTAL_RANGE_BITS))
+            stride = self.lm_format + int(lib.encx_ac_encode_capacity(n * K, TOTAL_RANGE_BITS))
             b = self._bufs[n] = dict(
                 codes=torch.zeros(B, K, n, dtype=torch.int64, device=dev),
                 lohi=torch.zeros(B, n, K, 2, dtype=torch.int32, device=dev),
@@ -640,17 +685,27 @@ class LMStreamEncoder(_LMSlots):
         b = self._buf(n)
         x = self._rows(n, n, b['codes'], None)
         b['err'].zero_()
-        self.lm._heads(x, self.B, n, self.K, probas=b['probas'], cdf=b['cdf'], sym=b['codes'], lohi=b['lohi'],
-                       err=b['err'])
-        call('encx_ac_encode_slots', b['lohi'].data_ptr(), self.B, n, self.K, self._slots.data_ptr(),
-             TOTAL_RANGE_BITS, b['out'].data_ptr(), b['out'].shape[1], b['nbytes'].data_ptr(),
-             b['serr'].data_ptr(), stream())
+        if self.lm_format == 2:
+            self._heads_nq(x, n, n, None, probas=b['probas'], cdf=b['cdf'], sym=b['codes'], lohi=b['lohi'],
+                           err=b['err'])
+            call('encx_ac_encode_slots_nq', b['lohi'].data_ptr(), self.B, n, self.K, self._slots.data_ptr(),
+                 self._nq.data_ptr(), TOTAL_RANGE_BITS, b['out'].data_ptr(), b['out'].shape[1],
+                 b['nbytes'].data_ptr(), b['serr'].data_ptr(), stream())
+        else:
+            self.lm._heads(x, self.B, n, self.K, probas=b['probas'], cdf=b['cdf'], sym=b['codes'], lohi=b['lohi'],
+                           err=b['err'])
+            call('encx_ac_encode_slots', b['lohi'].data_ptr(), self.B, n, self.K, self._slots.data_ptr(),
+                 TOTAL_RANGE_BITS, b['out'].data_ptr(), b['out'].shape[1], b['nbytes'].data_ptr(),
+                 b['serr'].data_ptr(), stream())
         self._advance(n, b['codes'])
 
     @torch.no_grad()
-    def packets(self, codes: torch.Tensor, frames: tp.Sequence[int]) -> tp.List[bytes]:
-        """One packet (header byte + coded payload) per slot, b'' for a slot with 0 frames."""
+    def packets(self, codes: torch.Tensor, frames: tp.Sequence[int],
+                n_q: tp.Optional[tp.Sequence[int]] = None) -> tp.List[bytes]:
+        """One packet (header + coded payload) per slot, b'' for a slot with 0 frames. The header is
+        the byte n, and with lm_format=2 the bytes (n, n_q[b])."""
         frames, n_max = self._check_frames(frames)
+        n_q = self._check_n_q(frames, n_q)
         if codes.dim() != 3 or tuple(codes.shape) != (self.B, self.K, n_max) or codes.dtype != torch.int64:
             raise ValueError(f'encx LM streaming: expected int64 codes [{self.B}, {self.K}, max(frames) = {n_max}], '
                              f'got {codes.dtype} {tuple(codes.shape)}')
@@ -658,7 +713,7 @@ class LMStreamEncoder(_LMSlots):
             raise RuntimeError('encx LM streaming takes device tensors (no CPU fallback)')
         self._ensure()
         b = self._buf(n_max)
-        g = self._run(n_max, self._body, frames)
+        g = self._run(n_max, self._body, frames, n_q)
         # the graph's own input; past a slot's count whatever the caller left becomes code 0
         keep = (self._cols[:n_max] < self._slots[:, :1]).unsqueeze(1)
         b['codes'].copy_(torch.where(keep, codes, 0))
@@ -680,9 +735,10 @@ class LMStreamEncoder(_LMSlots):
             raise RuntimeError(f'encx arithmetic coder failed: {e}')
         return [host[s, :nb[s]].numpy().tobytes() for s in range(self.B)]
 
-    def encode_slots(self, codes: torch.Tensor, frames: tp.Sequence[int]) -> tp.List[bytes]:
-        """The coded payloads (the packets without their header byte)."""
-        return [p[1:] for p in self.packets(codes, frames)]
+    def encode_slots(self, codes: torch.Tensor, frames: tp.Sequence[int],
+                     n_q: tp.Optional[tp.Sequence[int]] = None) -> tp.List[bytes]:
+        """The coded payloads (the packets without their header: one byte, two with lm_format=2)."""
+        return [p[self.lm_format:] for p in self.packets(codes, frames, n_q)]
 
 
 class LMStreamDecoder(_LMSlots):
@@ -692,10 +748,15 @@ class LMStreamDecoder(_LMSlots):
     codes, for one row per slot; it is captured once and replayed max(frames) times with the step
     in a device counter. A packet the coder cannot decode (it runs dry, or no interval holds the
     value) is data, not an error: that slot comes back with zero codes, is listed in `failed`, and
-    refuses further packets until restart([b]); the other slots are not disturbed."""
+    refuses further packets until restart([b]); the other slots are not disturbed.
 
-    def __init__(self, lm, batch: int, K: int, max_frames: int = 8, graphs: bool = True):
-        super().__init__(lm, batch, K, max_frames, graphs)
+    lm_format=2: decode_slots(payloads, frames, n_q), the payloads without their two header bytes;
+    rows k >= n_q[b] of the codes are zero. A payload may be empty, and bits past its end read as
+    zero, so the coder never runs dry: a truncated packet either fails (no interval holds the value)
+    or decodes to other codes, and integrity is the transport's job (include/encx.h)."""
+
+    def __init__(self, lm, batch: int, K: int, max_frames: int = 8, graphs: bool = True, lm_format: int = 1):
+        super().__init__(lm, batch, K, max_frames, graphs, lm_format)
         self.cap = int(lib.encx_ac_encode_capacity(self.max_frames * self.K, TOTAL_RANGE_BITS))
 
     def _ensure(self):
@@ -714,17 +775,26 @@ class LMStreamDecoder(_LMSlots):
     def _body(self, _key):
         B, K, M = self.B, self.K, self.max_frames
         x = self._rows(1, M, None, self._step)
-        self.lm._heads(x, B, 1, K, cdf=self._cdf)
         st = stream()
-        call('encx_ac_decode_slots', self._data.data_ptr(), self.cap, self._nbytes.data_ptr(), B,
-             self._dstate.data_ptr(), self._cdf.data_ptr(), K, self.lm.card, TOTAL_RANGE_BITS,
-             self._codes.data_ptr(), K * M, M, 1, M, self._step.data_ptr(), self._slots.data_ptr(),
-             self._prev.data_ptr(), self._err.data_ptr(), st)
+        if self.lm_format == 2:
+            self._heads_nq(x, 1, M, self._step, cdf=self._cdf)
+            call('encx_ac_decode_slots_nq', self._data.data_ptr(), self.cap, self._nbytes.data_ptr(), B,
+                 self._dstate.data_ptr(), self._cdf.data_ptr(), K, self.lm.card, TOTAL_RANGE_BITS,
+                 self._codes.data_ptr(), K * M, M, 1, M, self._step.data_ptr(), self._slots.data_ptr(),
+                 self._nq.data_ptr(), self._prev.data_ptr(), self._err.data_ptr(), st)
+        else:
+            self.lm._heads(x, B, 1, K, cdf=self._cdf)
+            call('encx_ac_decode_slots', self._data.data_ptr(), self.cap, self._nbytes.data_ptr(), B,
+                 self._dstate.data_ptr(), self._cdf.data_ptr(), K, self.lm.card, TOTAL_RANGE_BITS,
+                 self._codes.data_ptr(), K * M, M, 1, M, self._step.data_ptr(), self._slots.data_ptr(),
+                 self._prev.data_ptr(), self._err.data_ptr(), st)
         call('encx_lm_step_advance', self._step.data_ptr(), 1, st)
 
     @torch.no_grad()
-    def decode_slots(self, payloads: tp.Sequence[bytes], frames: tp.Sequence[int]):
+    def decode_slots(self, payloads: tp.Sequence[bytes], frames: tp.Sequence[int],
+                     n_q: tp.Optional[tp.Sequence[int]] = None):
         frames, n_max = self._check_frames(frames)
+        n_q = self._check_n_q(frames, n_q)
         if len(payloads) != self.B:
             raise ValueError(f'encx LM streaming: payloads for {len(payloads)} slots, the session has {self.B}')
         for b, (p, f) in enumerate(zip(payloads, frames)):
@@ -740,7 +810,7 @@ class LMStreamDecoder(_LMSlots):
         for b, p in enumerate(payloads):
             if len(p):
                 host[b, :len(p)] = torch.frombuffer(bytearray(p), dtype=torch.uint8)
-        g = self._run(0, self._body, frames)
+        g = self._run(0, self._body, frames, n_q)
         self._data.copy_(host)
         self._nbytes.copy_(torch.tensor([len(p) for p in payloads], dtype=torch.int64))
         self._codes.zero_()

@@ -60,8 +60,21 @@ The counts live in a device table beside the slot table, so one captured graph s
 The quantizer of such a step is one launch for all slots and layers (csrc/stream_rvq.hip): a
 column's whole residual chain runs in one workgroup with n_q[b] as its loop bound, and the codes
 are, bit for bit, rows [:n_q[b]] of the codes at the session's full bandwidth. Packets of such a
-step carry a second header byte with K (StreamPacker / StreamUnpacker(..., slot_n_q=True));
-their LM-coded form is not supported. The fused quantizer takes codebooks of bins a multiple
+step carry a second header byte with K: raw with StreamPacker / StreamUnpacker(..., slot_n_q=True),
+LM-coded with (..., use_lm=True, lm_format=2):
+
+    packer = StreamPacker(model, 64, 32, use_lm=True, lm_format=2)     # and the StreamUnpacker alike
+    packets = packer.pack_slots(codes, frames, nq)    # bytes (n, K) + one coder run, short flush
+    codes, frames, nq = unpacker.unpack_slots(packets)   # ready for dec.decode_slots(codes, frames, n_q=nq)
+
+The LM of such a stream (include/encx.h, packet format 2): the row of a frame sums the embeddings
+of the K codebooks its packet carries; codebook k enters with 1 + its code in the previous frame,
+or with the start index 0 where the previous frame did not carry k (or at the stream's start);
+heads, cdfs and coder symbols exist for k < K only. A stream that stays at K = k is coded with the
+cdf rows of a K = k session, bit for bit. The coder run ends with the short flush (the shortest
+value inside the final interval, trailing zero bytes dropped; the decoder reads zero bits past
+the end), so a truncated packet is not detected as "ran dry": it fails only if no interval holds
+the value, and otherwise decodes to wrong codes; integrity is the transport's job. The fused quantizer takes codebooks of bins a multiple
 of 4 and a latent dimension a multiple of 8 (up to 256); a session of any other model is built
 and streams as before, and only its steps that pass n_q are refused (NotImplementedError, a
 host check: check_rvq_shape).
@@ -958,10 +971,15 @@ class _Packets:
     variable-bandwidth packets (two header bytes, K per slot from an nq table); n_q is then the
     largest K."""
 
-    def __init__(self, model, batch, n_q, use_lm, lm, max_frames, graphs, lm_session, slot_n_q=False):
+    def __init__(self, model, batch, n_q, use_lm, lm, max_frames, graphs, lm_session, slot_n_q=False, lm_format=1):
         if use_lm and slot_n_q:
-            _refuse('LM-coded packets with a per-slot n_q (use_lm=True with slot_n_q=True)')
-        self.slot_n_q = bool(slot_n_q)
+            _refuse('LM-coded packets with a per-slot n_q are not slot_n_q=True (the raw two-byte-header form) '
+                    'with use_lm=True: pass use_lm=True, lm_format=2')
+        if lm_format not in (1, 2):
+            raise ValueError(f'encx streaming: lm_format {lm_format!r} (1 or 2)')
+        if lm_format == 2 and not use_lm:
+            raise ValueError('encx streaming: lm_format=2 is an LM-coded packet: it goes with use_lm=True')
+        self.slot_n_q, self.lm_format = bool(slot_n_q), int(lm_format)
         if not 1 <= batch <= MAX_BATCH:
             raise ValueError(f'encx streaming: batch {batch} (1..{MAX_BATCH})')
         if not 1 <= n_q <= min(model.quantizer.n_q, 64):
@@ -974,7 +992,7 @@ class _Packets:
         self._lm = None
         if self.use_lm:
             self._lm = lm_session(lm if lm is not None else model.get_lm_model(), self.B, self.n_q,
-                                  self.max_frames, graphs)
+                                  self.max_frames, graphs, lm_format=self.lm_format)
         self._dev = None
 
     def reset(self):
@@ -1029,12 +1047,14 @@ class StreamPacker(_Packets):
     Raw: header byte + the bit-packed codes, ONE launch for all slots whatever their counts.
     use_lm=True: header byte + one arithmetic-coder run under `lm` (model.get_lm_model() when
     None), the LM's context carried across a slot's packets (encx.lm.LMStreamEncoder). The
-    packet format is documented in include/encx.h. Slot b's codes past frames[b] are not read."""
+    packet format is documented in include/encx.h. Slot b's codes past frames[b] are not read.
+    use_lm=True, lm_format=2: pack_slots(codes, frames, n_q), the LM-coded packet with a codebook
+    count per slot and step (two header bytes, short flush; n_q is then the session's largest)."""
 
     def __init__(self, model, batch: int, n_q: int, use_lm: bool = False, lm=None, max_frames: int = 8,
-                 graphs: bool = True, slot_n_q: bool = False):
+                 graphs: bool = True, slot_n_q: bool = False, lm_format: int = 1):
         from .lm import LMStreamEncoder
-        super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamEncoder, slot_n_q)
+        super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamEncoder, slot_n_q, lm_format)
 
     @torch.no_grad()
     def pack_slots(self, codes: torch.Tensor, frames: tp.Sequence[int],
@@ -1042,10 +1062,10 @@ class StreamPacker(_Packets):
         """slot_n_q=True: pack_slots(codes, frames, n_q) -> variable-bandwidth packets (include/encx.h):
         bytes (frames[b], n_q[b]) and the payload of codes[b, :n_q[b], :frames[b]]; rows k >= n_q[b]
         are not read."""
-        if self.slot_n_q != (n_q is not None):
-            raise ValueError('encx streaming: n_q goes with slot_n_q=True, and only with it')
+        if (self.slot_n_q or self.lm_format == 2) != (n_q is not None):
+            raise ValueError('encx streaming: n_q goes with slot_n_q=True or lm_format=2, and only with them')
         if self._lm is not None:
-            return self._lm.packets(codes, frames)
+            return self._lm.packets(codes, frames, n_q)
         frames = _ints(frames, 'frames')
         n_max, _ = check_frames([True] * self.B, frames, 1, self.max_frames)
         if n_q is not None:
@@ -1083,12 +1103,15 @@ class StreamUnpacker(_Packets):
     """The inverse of StreamPacker: unpack_slots(packets) -> (codes [B, n_q, max(frames)] int64 on
     the GPU, zero past each slot's count, and frames), ready for StreamDecoder.decode_slots. A slot
     with nothing to deliver passes b''. A bad LM packet is data: its slot comes back with 0 frames
-    and zero codes, is listed in `failed`, and refuses packets until restart([b])."""
+    and zero codes, is listed in `failed`, and refuses packets until restart([b]).
+    use_lm=True, lm_format=2: -> (codes [B, n_q, max(frames)], frames, n_q) from the LM-coded
+    packets with a count per slot, ready for StreamDecoder.decode_slots(codes, frames, n_q=n_q); a
+    failed slot comes back with 0 frames, 0 codebooks and zero codes."""
 
     def __init__(self, model, batch: int, n_q: int, use_lm: bool = False, lm=None, max_frames: int = 8,
-                 graphs: bool = True, slot_n_q: bool = False):
+                 graphs: bool = True, slot_n_q: bool = False, lm_format: int = 1):
         from .lm import LMStreamDecoder
-        super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamDecoder, slot_n_q)
+        super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamDecoder, slot_n_q, lm_format)
 
     @property
     def failed(self) -> tp.List[int]:
@@ -1131,7 +1154,11 @@ class StreamUnpacker(_Packets):
                 if not 1 <= K <= self.n_q:
                     raise ValueError(f'encx streaming: the packet of slot {b} announces {K} codebooks '
                                      f'(1..n_q={self.n_q})')
-                if len(p) != packet_bytes_nq(n, K, self.bits):
+                if self.lm_format == 2:
+                    if len(p) - 2 > self._lm.cap:
+                        raise ValueError(f'encx streaming: a payload of {len(p) - 2} bytes in slot {b}; no packet of '
+                                         f'up to {self.max_frames} frames has more than {self._lm.cap}')
+                elif len(p) != packet_bytes_nq(n, K, self.bits):
                     raise ValueError(f'encx streaming: a packet of {n} frames of {K} codebooks in slot {b} has '
                                      f'{packet_bytes_nq(n, K, self.bits)} bytes, not {len(p)}')
             frames.append(int(n))
@@ -1152,6 +1179,11 @@ class StreamUnpacker(_Packets):
         """slot_n_q=True: -> (codes [B, n_q, max(frames)], frames, n_q) from variable-bandwidth
         packets, n_q[b] = 0 for an empty packet and zero rows at k >= n_q[b]: ready for
         StreamDecoder.decode_slots(codes, frames, n_q)."""
+        if self.lm_format == 2:
+            frames, n_q = self._headers_nq(packets)
+            codes, failed = self._lm.decode_slots([bytes(p[2:]) for p in packets], frames, n_q)
+            return (codes, [0 if b in failed else f for b, f in enumerate(frames)],
+                    [0 if b in failed else q for b, q in enumerate(n_q)])
         if self.slot_n_q:
             frames, n_q = self._headers_nq(packets)
             n_max = max(frames)

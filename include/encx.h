@@ -870,7 +870,8 @@ int encx_bitunpack_slots(const uint8_t* in, int64_t in_stride, int64_t B, int64_
  *   byte 1     K  (1..64 codebooks, at most the receiving session's K_max)
  *   payload    the n*K codes, t-major then codebook, `bits` bits each: encx_bitpack_bytes(n*K, bits)
  *              bytes, byte for byte the payload of a one-byte-header raw packet of K codebooks.
- * The one-byte-header packet stays the default; there is no LM-coded form with a per-slot K.
+ * The one-byte-header packet stays the default. The LM-coded form with a per-slot K is packet
+ * format 2 (below, after the LM over slots).
  *
  * The quantizer itself runs as ONE launch per direction (csrc/stream_rvq.hip): columns are
  * independent and code k depends only on layers < k, so a column's whole residual chain runs inside
@@ -962,6 +963,73 @@ int encx_ac_decode_slots(const uint8_t* data, int64_t stride, const int64_t* nby
                          const int32_t* cdf, int64_t K, int64_t card, int total_range_bits, int64_t* codes,
                          int64_t c_s, int64_t c_k, int64_t c_t, int64_t n_max, const int64_t* dev_step,
                          const int32_t* slots, int64_t* prev, int* err, encx_stream_t stream);
+
+/* ------------------------------ LM-coded packets with a K per slot and step (encx/lm.py lm_format=2)
+ * PACKET FORMAT 2.
+ *   byte 0     n  (1..max_frames <= 255 latent frames)
+ *   byte 1     K  (1..K_max codebooks of this packet)
+ *   payload    one arithmetic-coder run over the n*K codes, t-major then codebook, total_range_bits 24,
+ *              the cdfs of build_stable_quantized_cdf exactly as the LM form above, ended by the SHORT
+ *              FLUSH; may be empty.
+ * SHORT FLUSH. After the last symbol the coder holds low <= high and W = max_bit + 1 pending bits
+ * (oracle/ac_oracle.encode). With j the largest of 0..W for which v = ceil(low / 2^j) 2^j <= high, the
+ * W bits of v are appended most significant first (j = 0, v = low, is the reference's flush), the
+ * bits are packed as BitPacker(bits=1) packs them, and trailing zero bytes are dropped. The decoder
+ * reads zero bits past the end of a payload, so it sees a value inside [low, high] and decodes the
+ * same symbols. The transport carries the packet's length, as before.
+ * Consequence: "the coder ran dry" does not exist as a failure in format 2. A truncated packet decodes
+ * to wrong codes unless no interval holds the value (the one error the decoder still reports);
+ * integrity is the transport's job. The one-byte-header LM form and both raw forms are unchanged.
+ *
+ * LM SEMANTICS. A packet of K codebooks for slot b covers stream frames s .. s+n-1. The LM row of
+ * frame t is sum_{k<K} emb[k][idx_k], then the norm and the position term as above, with idx_k = 1 +
+ * code_k(t-1) if frame t-1 carried codebook k, and 0 (the start index) if it did not or t is the
+ * stream's first frame; codebooks k >= K of frame t-1 are dropped. Heads, cdfs and coder symbols
+ * exist for k < K only. So prev[b][k] becomes 0 for k >= nq[b] when a packet ends, on both sides.
+ * Position, ring and layers do not depend on K: encx_lm_layer_slots serves as it is. A stream that
+ * keeps K = k in a K_max session gets the cdf rows of a K = k session, bit for bit.
+ *
+ * Every entry below reads the slot table and int32 nq[B] (clamped to 0..K, K = K_max the row count
+ * of prev, codes, cdf and lohi), never forms an address from a slot's unread tail or from rows k >=
+ * nq[b], and returns ENCX_EINVAL before any launch for a NULL pointer or B, K outside 1..64, n_max
+ * outside 1..255, T outside 1..n_max.
+ * encx_lm_input_slots_nq / encx_lm_slots_advance_nq: encx_lm_input_slots / encx_lm_slots_advance with
+ * nq[b] as the row's codebook bound; the advance sets prev[b][k] = 0 for k >= nq[b] (codes or not).
+ * encx_lm_heads_slots: the heads, softmax, quantized cdf and (with sym) coding intervals of a slots
+ * step, x [B*T][D] -> probas / cdf [B][T][K][card], lohi [B][T][K][2], for the live rows (t +
+ * *dev_step < count) and k < nq[b] only: nothing is written for any other (row, k). A computed
+ * element runs encx_lm_heads's own chain (ascending-k fmaf from 0, never split; the same softmax and
+ * cdf code), so its bits are those of encx_lm_heads. A workgroup whose (row tile, column tile) holds
+ * no live row that uses one of its codebooks loads no weight and issues no FMA; a column tile that
+ * straddles two codebooks (card not a multiple of the tile) is computed if either is wanted. Up to
+ * 64 rows run on the VALU kernel (8-row tiles), more on the MFMA tiles, as encx_lm_heads. work:
+ * encx_lm_heads_workspace(B*T, K, card) bytes.
+ * encx_ac_encode_slots_nq: slot b pushes the first nq[b] intervals of each of its first count rows of
+ * lohi [B][n_max][K][2], ends with the short flush and writes (n, nq[b], payload) at out +
+ * b*out_stride; nbytes[b] = 2 + the payload's length, 0 for a slot that sits out (out_stride >= 2 +
+ * encx_ac_encode_capacity(n_max*K, bits) suffices). err[b] as encx_ac_encode_slots.
+ * encx_ac_decode_slots_nq: encx_ac_decode_slots over nq[b] symbols a step, reading zero bits past
+ * nbytes[b]; writes codes for k < nq[b] and 0 for the other k, prev[b][k] = symbol + 1 for k < nq[b]
+ * and 0 for the others. err[b]: 2 when no interval holds the value (never 1). */
+int encx_lm_input_slots_nq(const int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t, int64_t B, int64_t K,
+                           int64_t T, int64_t n_max, const int32_t* slots, const int32_t* nq, const int64_t* pos,
+                           const int64_t* prev, const int64_t* dev_step, const float* emb, int64_t card1, int64_t D,
+                           const float* ln_w, const float* ln_b, float max_period, float* x, encx_stream_t stream);
+int encx_lm_slots_advance_nq(const int32_t* slots, const int32_t* nq, int64_t B, int64_t K, int64_t n_max,
+                             int64_t* pos, int64_t* prev, const int64_t* codes, int64_t s_b, int64_t s_k,
+                             int64_t s_t, int64_t card1, encx_stream_t stream);
+int encx_lm_heads_slots(const float* x, int64_t B, int64_t T, int64_t n_max, int64_t D, const float* w,
+                        const float* bias, int64_t K, int64_t card, const int32_t* slots, const int32_t* nq,
+                        const int64_t* dev_step, float* work, float* probas, int32_t* cdf, int total_range_bits,
+                        float roundoff, int min_range, const int64_t* sym, int64_t s_b, int64_t s_k, int64_t s_t,
+                        int32_t* lohi, int* err, encx_stream_t stream);
+int encx_ac_encode_slots_nq(const int32_t* lohi, int64_t B, int64_t n_max, int64_t K, const int32_t* slots,
+                            const int32_t* nq, int total_range_bits, uint8_t* out, int64_t out_stride,
+                            int64_t* nbytes, int* err, encx_stream_t stream);
+int encx_ac_decode_slots_nq(const uint8_t* data, int64_t stride, const int64_t* nbytes, int64_t B, int64_t* state,
+                            const int32_t* cdf, int64_t K, int64_t card, int total_range_bits, int64_t* codes,
+                            int64_t c_s, int64_t c_k, int64_t c_t, int64_t n_max, const int64_t* dev_step,
+                            const int32_t* slots, const int32_t* nq, int64_t* prev, int* err, encx_stream_t stream);
 
 #ifdef __cplusplus
 }

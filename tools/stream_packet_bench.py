@@ -23,7 +23,20 @@ steps on first-order Markov code streams, then 4 unseen streams of 480 frames:
   (c) each stream as one coder run (lm.encode_streams of the whole stream).
 (a) - (c) is what flushing per packet costs, (b) - (a) what carrying the state buys.
 
+Bandwidth per slot (--nq). LM-coded packets of format 2 (a codebook count per slot and step, the
+short flush; include/encx.h) at B = 64, n in {1, 8}, K_max in {8, 32}, pack and unpack, graphs:
+  (a) format 2, every slot at K_max;   (b) format 2, slots cycling through 2, 4, .., K_max;
+  (c) format 2, every slot at 2;       (d) format 1 at K_max, the code before format 2: the baseline.
+Same clock and rounds; the unpackers consume a pre-coded sequence of 96 steps. Recorded with every
+row: (d)'s spread (max - min) / median, whether (a) is within that spread of (d), and whether (c)
+is faster than (a) by more than it. Bytes: the trained toy LM's payload bytes per frame for format
+2, format 1 and raw at n = 1 and n = 8; a format-2 payload longer than the format-1 payload of the
+same packet stops the tool.
+
 python tools/stream_packet_bench.py [--rounds 5] [--out profiles/stream/stream_packets.json]
+python tools/stream_packet_bench.py --nq [--out profiles/stream/stream_packets_nq.json]
+python tools/stream_packet_bench.py --nq --trace   # only 20 eager pack + unpack steps of (a) and of (d) at
+                                                   # B = 64, n = 8, K_max = 32, for a kernel trace of its own
 python tools/stream_packet_bench.py --trace   # only 20 LM steps and 20 raw packs at B = 64, n = 1,
                                               # for a kernel trace of its own
 """
@@ -150,6 +163,76 @@ def real_time(torch, m, lm, args, B=64):
             'lm_total_ms': round(coded, 4), 'lm_share_of_period': round(coded / period, 4), 'lm_met': coded < period}
 
 
+NQ_SEQ = 96  # pre-coded steps an --nq unpacker consumes before its slots restart
+
+
+def nq_row(torch, m, lm, B, n, kmax, args):
+    """One (n, K_max) row of --nq: variants a, b, c (format 2) and d (format 1), pack and unpack."""
+    from encx.streaming import StreamPacker, StreamUnpacker
+    dev = next(m.parameters()).device
+    g = torch.Generator().manual_seed(100 * kmax + n)
+    frames = [n] * B
+    codes = torch.randint(0, CARD, (B, kmax, n), generator=g).to(dev)
+    tables = {'a_f2_all_kmax': [kmax] * B,
+              'b_f2_cycling': [2 * (1 + b % (kmax // 2)) for b in range(B)],
+              'c_f2_all_2': [2] * B,
+              'd_f1_kmax': None}
+    v = {}
+    for name, nq in tables.items():
+        kw = dict(use_lm=True, lm=lm) if nq is None else dict(use_lm=True, lm=lm, lm_format=2)
+        extra = () if nq is None else (nq,)
+        lp, lu = StreamPacker(m, B, kmax, **kw), StreamUnpacker(m, B, kmax, **kw)
+        seq = [lp.pack_slots(torch.randint(0, CARD, (B, kmax, n), generator=g).to(dev), frames, *extra)
+               for _ in range(NQ_SEQ)]
+        state = {'i': 0}
+
+        def unpack(lu=lu, seq=seq, state=state):
+            if state['i'] == NQ_SEQ:
+                lu.restart(range(B))
+                state['i'] = 0
+            assert lu.unpack_slots(seq[state['i']])[1] == frames
+            state['i'] += 1
+
+        v[f'pack_{name}'] = lambda lp=lp, extra=extra: lp.pack_slots(codes, frames, *extra)
+        v[f'unpack_{name}'] = unpack
+    row = {'B': B, 'n': n, 'K_max': kmax}
+    row.update(measure(torch, v, args.rounds, args.min_seconds))
+    for side in ('pack', 'unpack'):
+        a, c, d = (row[f'{side}_{k}'] for k in ('a_f2_all_kmax', 'c_f2_all_2', 'd_f1_kmax'))
+        spread = (d['max'] - d['min']) / d['ms']
+        row[f'{side}_d_spread'] = round(spread, 4)
+        row[f'{side}_a_over_d'] = round(a['ms'] / d['ms'], 4)
+        row[f'{side}_a_within_spread_of_d'] = a['ms'] <= d['ms'] * (1 + spread)
+        row[f'{side}_c_gain_over_a'] = round(1 - c['ms'] / a['ms'], 4)
+        row[f'{side}_c_faster_than_a_by_more_than_spread'] = 1 - c['ms'] / a['ms'] > spread
+    return row
+
+
+def nq_bytes(torch, dev, steps=300, B=4, T=480):
+    """The trained toy LM of bytes_section: payload bytes per frame of format 2, format 1 and raw."""
+    from encx.lm import LMStreamEncoder
+    lm, codes, loss = toy_lm(torch, dev, steps, B, T)
+    res = {'lm': '1 x 64, dim 64, 1 layer, past_context 20', 'train_steps': steps,
+           'final_nll_nats_per_code': round(loss, 4), 'streams': B, 'frames_per_stream': T}
+    per = lambda nbytes: round(nbytes / (B * T), 4)
+    for n in (1, 8):
+        e1, e2 = LMStreamEncoder(lm, B, 1, max_frames=8), LMStreamEncoder(lm, B, 1, max_frames=8, lm_format=2)
+        f1 = f2 = 0
+        for t in range(0, T, n):
+            chunk = codes[:, :, t:t + n].contiguous()
+            p1, p2 = e1.encode_slots(chunk, [n] * B), e2.encode_slots(chunk, [n] * B, [1] * B)
+            for a, b in zip(p1, p2):
+                if len(b) > len(a):
+                    raise SystemExit(f'a format-2 payload of {len(b)} bytes against {len(a)} in format 1')
+            f1, f2 = f1 + sum(map(len, p1)), f2 + sum(map(len, p2))
+        packets = B * T // n
+        res[f'n{n}'] = {'format2_payload': per(f2), 'format1_payload': per(f1), 'raw_payload': per(-(-n * 6 // 8) * packets),
+                        'format2_with_header': per(f2 + 2 * packets), 'format1_with_header': per(f1 + packets),
+                        'raw_with_header': per((1 + -(-n * 6 // 8)) * packets),
+                        'saved_bytes_per_packet': round((f1 - f2) / packets, 4)}
+    return res
+
+
 def markov(torch, B, T, seed):
     perm = torch.randperm(64, generator=torch.Generator().manual_seed(1234))
     g = torch.Generator().manual_seed(seed)
@@ -161,8 +244,9 @@ def markov(torch, B, T, seed):
     return c
 
 
-def bytes_section(torch, dev, steps=300, B=4, T=480):
-    from encx.lm import LMModel, LMStreamEncoder
+def toy_lm(torch, dev, steps, B, T):
+    """The small LM of the bytes sections, trained here -> (lm, unseen streams [B, 1, T], final loss)."""
+    from encx.lm import LMModel
     from encx.optim import FlatAdam
     torch.manual_seed(77)
     lm = LMModel(1, 64, dim=64, num_heads=2, num_layers=1, past_context=20).to(dev)
@@ -175,9 +259,14 @@ def bytes_section(torch, dev, steps=300, B=4, T=480):
         opt.step()
     lm.invalidate_packed()
     lm.eval()
-    codes = markov(torch, B, T, 909).to(dev)
+    return lm, markov(torch, B, T, 909).to(dev), float(loss.detach())
+
+
+def bytes_section(torch, dev, steps=300, B=4, T=480):
+    from encx.lm import LMStreamEncoder
+    lm, codes, loss = toy_lm(torch, dev, steps, B, T)
     res = {'lm': '1 x 64, dim 64, 1 layer, past_context 20', 'train_steps': steps,
-           'final_nll_nats_per_code': round(float(loss.detach()), 4), 'streams': B, 'frames_per_stream': T,
+           'final_nll_nats_per_code': round(loss, 4), 'streams': B, 'frames_per_stream': T,
            'raw_bytes_per_frame': 6 / 8}
     per = lambda nbytes: round(nbytes / (B * T), 4)
     res['c_whole_stream_one_run'] = per(sum(len(d) for d in lm.encode_streams(codes)))
@@ -200,8 +289,11 @@ def main():
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--min-seconds', type=float, default=0.3)
     ap.add_argument('--trace', action='store_true', help='only a few B = 64, n = 1 steps, for a kernel trace')
-    ap.add_argument('--out', type=str, default=os.path.join(ROOT, 'profiles', 'stream', 'stream_packets.json'))
+    ap.add_argument('--nq', action='store_true', help='format-2 packets (a codebook count per slot) against format 1')
+    ap.add_argument('--out', type=str, default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'stream', 'stream_packets_nq.json' if args.nq else 'stream_packets.json')
 
     import torch
     if not torch.cuda.is_available():
@@ -219,6 +311,19 @@ def main():
     lm = LMModel(32, CARD, dim=200, num_layers=5, past_context=262).to(dev).eval()
 
     with torch.no_grad():
+        if args.trace and args.nq:
+            from encx.streaming import StreamPacker, StreamUnpacker
+            B, n, kmax = 64, 8, 32
+            frames, nq = [n] * B, [kmax] * B
+            codes = torch.randint(0, CARD, (B, kmax, n)).to(dev)
+            kw = dict(use_lm=True, lm=lm, graphs=False)
+            pa, ua = StreamPacker(m, B, kmax, lm_format=2, **kw), StreamUnpacker(m, B, kmax, lm_format=2, **kw)
+            pd, ud = StreamPacker(m, B, kmax, **kw), StreamUnpacker(m, B, kmax, **kw)
+            for _ in range(20):
+                ua.unpack_slots(pa.pack_slots(codes, frames, nq))
+                ud.unpack_slots(pd.pack_slots(codes, frames))
+            torch.cuda.synchronize()
+            return
         if args.trace:
             from encx.streaming import StreamPacker
             B, ones = 64, [1] * 64
@@ -229,6 +334,26 @@ def main():
                 lp.pack_slots(codes, ones)
             torch.cuda.synchronize()
             return
+        if args.nq:
+            rows = []
+            for kmax in (8, 32):
+                for n in (1, 8):
+                    rows.append(nq_row(torch, m, lm, 64, n, kmax, args))
+                    print(json.dumps(rows[-1]), flush=True)
+    if args.nq:
+        nbytes = nq_bytes(torch, dev)
+        print(json.dumps(nbytes), flush=True)
+        res = {'metric': 'ms per call (host copy of the packets included) and payload bytes per frame',
+               'device': torch.cuda.get_device_name(0), 'B': 64, 'bits': BITS,
+               'lm': '32 x 1024, dim 200, 5 layers, past_context 262, random weights', 'rounds': args.rounds,
+               'timing': f'host clock around blocks of calls ending in a synchronise, >= {args.min_seconds} s per '
+                         'variant, variants alternating within a round, after warm-up',
+               'rows': rows, 'bytes': nbytes}
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(json.dumps(res, indent=1) + '\n')
+        return
+    with torch.no_grad():
         rows = []
         for B in (1, 64):
             for n in (1, 8):
