@@ -23,7 +23,9 @@
 //                      to the lowest code, as the 64-bit atomicMin of rvq.hip), and x -= E[code]
 //                      exactly (rvq_apply with ste = 0). Three barriers a layer.
 //  stream_rvq_decode   grid (n_max, B): out[b][d][t] = ((E_0[c_0] + E_1[c_1]) + ...)[d] in
-//                      ascending k < nq[b], rvq_gather's order.
+//                      ascending k < nq[b], rvq_gather's order. With a concealment table
+//                      (encx_stream_rvq_decode_slots_conceal) the columns t < count of a lost slot
+//                      are copies of its held column instead, its codes and nq[b] unread.
 // Both read the slot table (count, first flag) and the nq table, clamp them, and never form an
 // address from a slot's unread tail (columns >= its count).
 #include "common.h"
@@ -204,6 +206,8 @@ struct SrDec {
     const int32_t* nq;
     float* out;
     int64_t o_b, o_d, o_t;
+    const int32_t* conceal;  // nullable: the concealment table [B][4] (encx.h), word 0 = the step is lost
+    const float* held;       // with it: held[b*o_b + d*o_d], the slot's last decoded latent column
 };
 
 constexpr int SR_KU = 8;  // gathers in flight per thread
@@ -215,6 +219,12 @@ __global__ __launch_bounds__(128) void stream_rvq_decode_kernel(SrDec a) {
     const int count = clampi(a.slots[2 * b], 0, a.n_max);
     const int nq = clampi(a.nq[b], 0, a.K_max);
     float* o = a.out + b * a.o_b + t * a.o_t;
+    const bool lost = a.conceal && t < count && a.conceal[4 * b] != 0;
+    if (lost) {  // the held latent: neither the slot's codes nor its nq are looked at
+        const float* h = a.held + b * a.o_b;
+        for (int d = threadIdx.x; d < a.D; d += blockDim.x) o[d * a.o_d] = h[d * a.o_d];
+        return;
+    }
     if (t >= count || nq == 0) {
         for (int d = threadIdx.x; d < a.D; d += blockDim.x) o[d * a.o_d] = 0.f;
         return;
@@ -293,7 +303,25 @@ int encx_stream_rvq_decode_slots(const int64_t* codes, int64_t c_b, int64_t c_k,
     ENCX_REQUIRE(sr_dims_ok(B, K_max, bins, D, n_max));
     encx_prof_scope ps((hipStream_t)stream, 1.0 * B * n_max * K_max * D,
                        4.0 * B * D * n_max * (K_max + 1) + 8.0 * B * K_max * n_max, "stream_rvq_decode", false);
-    SrDec a{codes, c_b, c_k, c_t, packed, (int)K_max, (int)bins, (int)D, (int)n_max, slots, nq, out, o_b, o_d, o_t};
+    SrDec a{codes, c_b, c_k, c_t, packed, (int)K_max, (int)bins, (int)D, (int)n_max, slots, nq, out, o_b, o_d, o_t,
+            nullptr, nullptr};
+    hipLaunchKernelGGL(stream_rvq_decode_kernel, dim3((unsigned)n_max, (unsigned)B), dim3(128), 0,
+                       (hipStream_t)stream, a);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
+
+int encx_stream_rvq_decode_slots_conceal(const int64_t* codes, int64_t c_b, int64_t c_k, int64_t c_t,
+                                         const float* packed, int64_t B, int64_t K_max, int64_t bins, int64_t D,
+                                         int64_t n_max, const int32_t* slots, const int32_t* nq,
+                                         const int32_t* conceal, const float* held, float* out, int64_t o_b,
+                                         int64_t o_d, int64_t o_t, encx_stream_t stream) {
+    ENCX_REQUIRE(codes && packed && slots && nq && conceal && held && out);
+    ENCX_REQUIRE(sr_dims_ok(B, K_max, bins, D, n_max));
+    encx_prof_scope ps((hipStream_t)stream, 1.0 * B * n_max * K_max * D,
+                       4.0 * B * D * n_max * (K_max + 1) + 8.0 * B * K_max * n_max, "stream_rvq_decode_conceal", false);
+    SrDec a{codes, c_b, c_k, c_t, packed, (int)K_max, (int)bins, (int)D, (int)n_max, slots, nq, out, o_b, o_d, o_t,
+            conceal, held};
     hipLaunchKernelGGL(stream_rvq_decode_kernel, dim3((unsigned)n_max, (unsigned)B), dim3(128), 0,
                        (hipStream_t)stream, a);
     ENCX_CHECK_LAUNCH();

@@ -759,6 +759,12 @@ class LMStreamDecoder(_LMSlots):
         super().__init__(lm, batch, K, max_frames, graphs, lm_format)
         self.cap = int(lib.encx_ac_encode_capacity(self.max_frames * self.K, TOTAL_RANGE_BITS))
 
+    def lose(self, slots):
+        """A packet of each named slot did not arrive: its context no longer matches the
+        sender's, so the slot is failed, exactly as after a bad packet, until restart([b])."""
+        from .streaming import check_restart
+        self.failed.update(check_restart(slots, self.B))
+
     def _ensure(self):
         if self._ready:
             return

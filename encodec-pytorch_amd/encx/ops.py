@@ -872,11 +872,20 @@ def stream_rvq_encode_slots(x, books, slots, nq, codes=None):
     return codes
 
 
-def stream_rvq_decode_slots(codes, books, slots, nq, out=None):
+def _conceal_table(B, conceal):
+    if not conceal.is_cuda or conceal.dtype != torch.int32 or tuple(conceal.shape) != (B, 4) \
+            or not conceal.is_contiguous():
+        raise ValueError(f'encx: conceal must be a contiguous int32 [{B}, 4] tensor on the GPU')
+
+
+def stream_rvq_decode_slots(codes, books, slots, nq, out=None, conceal=None, held=None):
     """ONE launch: out[b, :, t] = the sum of slot b's first nq[b] codebook rows at codes[b, k, t]
     in ascending k (rvq_decode's order), zero for t >= count. codes [B, K, n_max] int64 (rows k >=
     nq[b] and columns t >= count are not read; a code is clamped to the codebook), out [B, D,
-    n_max] fp32 with any strides (the decoder's first window)."""
+    n_max] fp32 with any strides (the decoder's first window).
+
+    conceal (int32 [B, 4]: lost, p, r, 0; encx.h) and held ([B, D, 1], the column before `out` in
+    its window): columns t < count of a lost slot are copies of held, its codes and nq unread."""
     B, K, n = codes.shape
     if not codes.is_cuda or codes.dtype != torch.int64 or K != books.K:
         raise ValueError(f'encx: expected int64 codes [B, {books.K}, n] on the GPU')
@@ -886,8 +895,44 @@ def stream_rvq_decode_slots(codes, books, slots, nq, out=None):
     if tuple(out.shape) != (B, books.D, n):
         raise ValueError(f'encx: out must be [{B}, {books.D}, {n}]')
     _check(out, 'out')
-    call('encx_stream_rvq_decode_slots', codes.data_ptr(), *codes.stride(), ptr(books.E), B, K, books.bins,
-         books.D, n, ptr(slots), ptr(nq), out.data_ptr(), *out.stride(), stream())
+    if conceal is None:
+        call('encx_stream_rvq_decode_slots', codes.data_ptr(), *codes.stride(), ptr(books.E), B, K, books.bins,
+             books.D, n, ptr(slots), ptr(nq), out.data_ptr(), *out.stride(), stream())
+        return out
+    _conceal_table(B, conceal)
+    _check(held, 'held')
+    if tuple(held.shape) != (B, books.D, 1) or held.stride()[:2] != out.stride()[:2]:
+        raise ValueError(f'encx: held must be [{B}, {books.D}, 1] with the strides of out')
+    call('encx_stream_rvq_decode_slots_conceal', codes.data_ptr(), *codes.stride(), ptr(books.E), B, K, books.bins,
+         books.D, n, ptr(slots), ptr(nq), ptr(conceal), held.data_ptr(), out.data_ptr(), *out.stride(), stream())
+    return out
+
+
+def stream_conceal_fill(win, P, n, slots, conceal):
+    """The held latent after the per-layer dequantizer: win [B, D, W] (the decoder's first window,
+    a view with stride 1 along its columns), rows of the lost slots get columns [P, P + count) <-
+    column P-1. One launch."""
+    _check(win, 'win')
+    B, D, W = win.shape
+    if win.stride(2) != 1 or P < 1 or W < P + n:
+        raise ValueError(f'encx: a window of {W} columns for a history of {P} and {n} frames')
+    _conceal_table(B, conceal)
+    call('encx_stream_conceal_fill', win.data_ptr(), win.stride(0), win.stride(1), B, D, P, n, ptr(slots),
+         ptr(conceal), stream())
+
+
+def stream_conceal_out(x, hop, n, slots, conceal, hold, fade, recover):
+    """The output of a concealed step: x [B, C, >= n * hop] (the decoder's last window, read in
+    place) -> [B, C, n * hop] contiguous, zero past each slot's count * hop, the fade ramp of the
+    concealment table elsewhere (encx.h). One launch."""
+    _check(x, 'x')
+    B, C, W = x.shape
+    if x.stride(2) != 1 or W < n * hop:
+        raise ValueError(f'encx: a window of {W} columns for {n} frames of {hop} samples')
+    _conceal_table(B, conceal)
+    out = torch.empty(B, C, n * hop, device=x.device, dtype=torch.float32)
+    call('encx_stream_conceal_out', x.data_ptr(), x.stride(0), x.stride(1), out.data_ptr(), B, C, hop, n,
+         ptr(slots), ptr(conceal), hold, fade, recover, stream())
     return out
 
 

@@ -90,7 +90,35 @@ on a ring cache, for a stream of any length (encx/lm.py LMStreamEncoder / LMStre
     packets = packer.pack_slots(codes, frames)        # list of bytes, b'' for a slot with 0 frames
     codes, frames = unpacker.unpack_slots(packets)    # ready for dec.decode_slots(codes, frames)
 
-A lost packet is not concealed: restart([b]) on both sides is the remedy.
+Lost packets. The packets are meant for a lossy link, and the decoder conceals a packet that
+did not arrive, per slot and on the device:
+
+    wav = dec.decode_slots(codes, frames, lost=[b in gone for b in range(64)])   # frames[b] to conceal
+    unpacker.lose([5])                       # LM-coded streams: slot 5's context is out of step
+
+A lost slot decodes its last latent frame again for frames[b] frames (the transport knows the
+count from timing; packet_frames(p) reads it from a packet that is held but cannot be decoded).
+That frame is column P-1 of the decoder's first window, where the end-of-step roll left it, so
+nothing is kept on the host and the result is, bit for bit, that of repeating the slot's last
+delivered code column with the codebook count it was decoded with. Everything behind the first
+window runs as in any step, so the slot's state stays continuous and it simply goes on with its
+next packet: no restart, no first chunk. Its codes and n_q[b] are not used.
+The output fades. Per slot two integers, p in 0..M (M = conceal_fade * conceal_recover * hop,
+starting at M) and r, the samples concealed in the current run; per output sample of a step
+    concealed   r += 1, and p = max(0, p - conceal_recover) once r > conceal_hold * hop
+    delivered   p = min(M, p + conceal_fade); r = 0 at the end of the step
+and a slot that sits out changes neither. The sample is x where p == M (after the sample's
+update), x * (float(p) * (1 / M)) in fp32 otherwise. With the defaults (hold 2, fade 6, recover 1
+frames: 27 ms held, 80 ms down, 13 ms back up at 75 frames/s) these are design choices, not
+tuned by ear. restart and reset put a slot back to p = M, r = 0. Steps with a lost slot, or with
+a slot below M, run graphs of their own, one per (n_max, any_first) whatever the loss pattern;
+every other step runs what it ran before. Refused: a lost slot that has not started or has 0
+frames (ValueError), a decoder whose first window keeps no history (NotImplementedError).
+LM-coded streams: after a lost packet the receiver's LM context differs from the sender's.
+unpacker.lose([b]) marks the slot failed and drops its packets unread (0 frames) while the decoder
+conceals; once the sender knows, packer.restart([b]) and unpacker.restart([b]) restart the LM
+context only. Encoder and decoder are NOT restarted. Not here: codes predicted by the LM for the
+lost frames, redundancy in the packets, sequence numbers (detecting a loss is the transport's job).
 
 Inference only. Weight-normed weights are prepared once, at construction; call
 refresh_weights() after changing the model. reset() restarts every slot.
@@ -321,6 +349,82 @@ def check_n_q(frames, n_q, n_q_max: int) -> tp.List[int]:
             raise ValueError(f'encx streaming: n_q {q} in slot {b} (1..{n_q_max})')
         out.append(q)
     return out
+
+
+MAX_FADE = 1 << 24  # the fade position is multiplied as an fp32: exact up to 2^24
+_R_CAP = 1 << 30    # r saturates here: past the hold only r > hold is ever asked of it
+
+
+def fade_span(hold_frames: int, fade_frames: int, recover_frames: int, hop: int) -> int:
+    """M = fade_frames * recover_frames * hop, the full level of the fade position p. A concealed
+    sample past the hold lowers p by recover_frames, a delivered one raises it by fade_frames, so the
+    way down takes fade_frames frames and the way up recover_frames. Raises ValueError; host only."""
+    hold_frames, fade_frames, recover_frames = (operator.index(v) for v in (hold_frames, fade_frames, recover_frames))
+    if not 0 <= hold_frames <= 255:
+        raise ValueError(f'encx streaming: conceal_hold {hold_frames} (0..255 frames)')
+    if not 1 <= fade_frames <= 255:
+        raise ValueError(f'encx streaming: conceal_fade {fade_frames} (1..255 frames)')
+    if not 1 <= recover_frames <= 255:
+        raise ValueError(f'encx streaming: conceal_recover {recover_frames} (1..255 frames)')
+    M = fade_frames * recover_frames * int(hop)
+    if M > MAX_FADE:
+        raise ValueError(f'encx streaming: a fade of {fade_frames} x {recover_frames} frames of {hop} samples has '
+                         f'{M} levels (at most 2^24)')
+    return M
+
+
+def check_lost(started: tp.Sequence[bool], frames: tp.Sequence[int], lost, M: int = 0) -> tp.Optional[tp.List[bool]]:
+    """lost[b]: slot b's packet of this step did not arrive, and frames[b] (1..max_frames, known to
+    the transport from timing) frames are concealed. -> the flags as bools, or None when no slot is
+    lost (lost=None, or all False). M: the session's fade span. Raises ValueError; host data only."""
+    if lost is None:
+        return None
+    try:
+        lost = [bool(v) for v in lost]
+    except TypeError:
+        raise ValueError('encx streaming: lost must be a sequence of bools') from None
+    if len(lost) != len(started) or len(frames) != len(started):
+        raise ValueError(f'encx streaming: lost for {len(lost)} slots, the session has {len(started)}')
+    if not any(lost):
+        return None
+    if M > MAX_FADE:
+        raise ValueError(f'encx streaming: a fade of {M} levels (at most 2^24)')
+    for b, (on, f, gone) in enumerate(zip(started, frames, lost)):
+        if not gone:
+            continue
+        if not f:
+            raise ValueError(f'encx streaming: slot {b} is lost with 0 frames (pass the frames to conceal)')
+        if not on:
+            raise ValueError(f'encx streaming: slot {b} is lost before its first chunk: there is nothing to repeat')
+    return lost
+
+
+def fade_positions(p: int, r: int, lost: bool, samples: int, hold: int, fade: int, recover: int, M: int):
+    """The fade position after each of a step's `samples` samples of one slot, in closed form, from
+    the slot's (p, r) at the start of the step; hold in samples. int64 [samples]. Per sample the
+    rule is: concealed r += 1, and p = max(0, p - recover) once r > hold; delivered p = min(M, p +
+    fade). The kernel (csrc/stream_conceal.hip) evaluates the same expressions."""
+    j1 = np.arange(1, samples + 1, dtype=np.int64)
+    if lost:
+        dec = np.maximum(r + j1 - hold, 0) - max(r - hold, 0)
+        return np.maximum(p - recover * dec, 0)
+    return np.minimum(p + fade * j1, M)
+
+
+def fade_step(p: int, r: int, lost: bool, samples: int, hold: int, fade: int, recover: int, M: int):
+    """(p, r) of a slot after a step of `samples` samples (0: it sat out, nothing changes)."""
+    if not samples:
+        return p, r
+    if lost:
+        dec = max(r + samples - hold, 0) - max(r - hold, 0)
+        return max(p - recover * dec, 0), min(r + samples, _R_CAP)
+    return min(p + fade * samples, M), 0
+
+
+def fade_gains(positions, M: int):
+    """The fp32 factor of each sample: float(p) * invM with invM = fp32(1) / fp32(M); where p == M
+    the sample is written unscaled (the factor is then not used)."""
+    return positions.astype(np.float32) * (np.float32(1) / np.float32(M))
 
 
 def check_restart(slots, batch: int) -> tp.List[int]:
@@ -814,11 +918,15 @@ class StreamDecoder:
     """Chunked decoder of a causal model for `batch` streams: decode(codes [B, n_q, n]) -> wav
     [B, C, n * hop_length]. See the module docstring."""
 
-    def __init__(self, model, batch: int, n_q: int, max_frames: int = 8, graphs: bool = True):
+    def __init__(self, model, batch: int, n_q: int, max_frames: int = 8, graphs: bool = True,
+                 conceal_hold: int = 2, conceal_fade: int = 6, conceal_recover: int = 1):
         plan = decoder_plan(model)
         self.n_q = int(n_q)
         if not 1 <= self.n_q <= model.quantizer.n_q:
             raise ValueError(f'encx streaming: n_q {n_q} (the model has {model.quantizer.n_q} codebooks)')
+        # the fade of a concealed slot (module docstring): frames held, frames down, frames back up
+        self._M = fade_span(conceal_hold, conceal_fade, conceal_recover, plan.hop_length)
+        self._hold, self._fade, self._recover = int(conceal_hold), int(conceal_fade), int(conceal_recover)
         self._s = _Session(model, plan, batch, max_frames, graphs)
         self.channels = model.channels
         self.bins = model.quantizer.bins
@@ -826,10 +934,24 @@ class StreamDecoder:
         self._codes: tp.Dict[int, torch.Tensor] = {}
         self._codes_nq: tp.Dict[int, torch.Tensor] = {}
         self._books = _books(self._embeds, False)  # a decoder gathers rows: no transpose, no |e|^2
+        # concealment: per slot the fade position p (0..M) and the samples r of the current loss run,
+        # advanced here exactly as the kernels do, and the table they read (encx.h: conceal[B][4]),
+        # uploaded as the slot table is; its graphs never replace one of the other paths
+        B, dev = self._s.B, self._s.dev
+        self._p, self._r = [self._M] * B, [0] * B
+        self._dirty = False  # some slot has p < M or r > 0
+        self._ct = torch.zeros(B, 4, device=dev, dtype=torch.int32)
+        self._ct_host: tp.Optional[tuple] = None
+        self._ct_staging = [(torch.zeros(B, 4, dtype=torch.int32).pin_memory(), torch.cuda.Event())
+                            for _ in range(4)]
+        self._ct_staged = 0
+        self._conceal_graphs: tp.Dict[tuple, tuple] = {}
         with torch.no_grad():
             self._s._warm(self._body, self._body_slots)
             if self._books is not None:
                 _warm_nq(self._s, self.n_q, self._body_nq)
+            if plan.windows[0].P:
+                self._warm_conceal()
 
     hop_length = property(lambda self: self._s.hop_length)
     min_first_frames = property(lambda self: self._s.min_first_frames)
@@ -837,16 +959,82 @@ class StreamDecoder:
 
     def reset(self):
         self._s.reset()
+        self._p, self._r, self._dirty = [self._M] * self._s.B, [0] * self._s.B, False
 
     def restart(self, slots):
-        """As StreamEncoder.restart."""
+        """As StreamEncoder.restart; the slots' fade starts over at full level."""
         self._s.restart(slots)
+        for b in check_restart(slots, self._s.B):
+            self._p[b], self._r[b] = self._M, 0
+        self._dirty = any(p < self._M or r for p, r in zip(self._p, self._r))
 
     def refresh_weights(self):
         self._s.refresh_weights()
         self._embeds = _embeds(self._s.model, self.n_q)
         if self._books is not None:
             self._books.prepare(self._embeds)
+
+    # ---- concealment
+    def _put_conceal(self, lost):
+        """Fill the device concealment table for this step (lost flag, p and r at its start), as
+        _Session.put_slots: only when it changed, through rotating pinned staging."""
+        tab = tuple((int(l), p, r, 0) for l, p, r in zip(lost, self._p, self._r))
+        if tab == self._ct_host:
+            return
+        buf, ev = self._ct_staging[self._ct_staged]
+        self._ct_staged = (self._ct_staged + 1) % len(self._ct_staging)
+        ev.synchronize()
+        buf.copy_(torch.tensor(tab, dtype=torch.int32))
+        self._ct.copy_(buf, non_blocking=True)
+        ev.record()
+        self._ct_host = tab
+
+    def _advance(self, frames, lost):
+        """p and r of every slot after the step, by the rule the output kernel applies per sample."""
+        if lost is None and not self._dirty:
+            return
+        hop = self._s.hop_length
+        for b, f in enumerate(frames):
+            self._p[b], self._r[b] = fade_step(self._p[b], self._r[b], bool(lost and lost[b]), f * hop,
+                                               self._hold * hop, self._fade, self._recover, self._M)
+        self._dirty = any(p < self._M or r for p, r in zip(self._p, self._r))
+
+    def _body_conceal(self, n, first, fused):
+        """A slots step with lost or fading slots. The latent of a lost slot is its held column
+        (P-1 of the first window), set by the fused dequantizer itself or, after the per-layer
+        one, by the fill kernel; the output kernel reads the last window in place, zeroes the
+        samples past each slot's count and applies the fade."""
+        s = self._s
+        P, win = s.plan.windows[0].P, s.bufs[0]
+        if fused:
+            ops.stream_rvq_decode_slots(self._code_buf_nq(n), self._books, s._slots, s._nq, win[:, :, P:P + n],
+                                        self._ct, win[:, :, P - 1:P])
+        else:
+            win[:, :, P:P + n].copy_(ops.rvq_decode(self._code_buf(n), self._embeds))
+            ops.stream_conceal_fill(win, P, n, s._slots, self._ct)
+        s._layers(n, first, slots=True)
+        return (ops.stream_conceal_out(s.bufs[s.plan.layers[-1].dst], s.hop_length, n, s._slots, self._ct,
+                                       self._hold, self._fade, self._recover),)
+
+    def _warm_conceal(self):
+        """Load the kernels of a concealed step before any capture, as _warm_nq does: a first chunk,
+        then one concealed frame for every slot on either dequantizer, eagerly; then a clean session."""
+        s = self._s
+        graphs, s.graphs = s.graphs, False
+        try:
+            frames = [s.min_first_frames] * s.B
+            s.put_slots(frames)
+            s._step_slots(frames, *s.check_frames(frames), self._body_slots)
+            frames = [1] * s.B
+            s.put_slots(frames)
+            self._put_conceal([True] * s.B)
+            self._body_conceal(1, False, False)
+            if self._books is not None:
+                s.put_nq([self.n_q] * s.B)
+                self._body_conceal(1, False, True)
+        finally:
+            s.graphs = graphs
+        s.reset()
 
     def _code_buf_nq(self, n):
         """The codes of a per-slot-bandwidth step as the caller passed them, [B, n_q, n]: the
@@ -909,7 +1097,7 @@ class StreamDecoder:
         s.check_frames([n] * s.B)
         if not codes.is_cuda:
             raise RuntimeError('encx streaming takes device tensors (no CPU fallback)')
-        if not s.uniform():  # some slots are on their first chunk, others not
+        if not s.uniform() or self._dirty:  # some slots are on their first chunk, or in a fade
             return self.decode_slots(codes, [n] * s.B)
         buf = self._code_buf(n)
         buf.copy_(codes.permute(1, 0, 2))
@@ -917,8 +1105,8 @@ class StreamDecoder:
         return s._step(n, self._body)[0]
 
     @torch.no_grad()
-    def decode_slots(self, codes: torch.Tensor, frames: tp.Sequence[int],
-                     n_q: tp.Optional[tp.Sequence[int]] = None) -> torch.Tensor:
+    def decode_slots(self, codes: tp.Optional[torch.Tensor], frames: tp.Sequence[int],
+                     n_q: tp.Optional[tp.Sequence[int]] = None, lost=None) -> torch.Tensor:
         """codes [B, n_q, n_max], frames[b] = the frames slot b delivers (0: it sits out), n_max =
         max(frames) -> wav [B, C, n_max * hop_length]. Slot b's codes past frames[b] are not read
         (code 0 is decoded in their place); its samples past frames[b] * hop_length are zero.
@@ -926,31 +1114,68 @@ class StreamDecoder:
 
         n_q: as StreamEncoder.encode_slots: B ints, the codebooks of each slot this step; rows
         k >= n_q[b] of slot b's codes are not read, and the slot's wave is that of a decoder built
-        for n_q[b] codebooks."""
+        for n_q[b] codebooks.
+
+        lost: B bools. A lost slot's packet did not arrive: frames[b] (1..max_frames, which the
+        transport knows from timing) frames are concealed by decoding the slot's last latent frame
+        again, bit for bit what repeating its last delivered code column would give, and its output
+        fades out after conceal_hold frames and back in once it delivers (module docstring). The
+        codes and n_q[b] of a lost slot are not used (anything may stand there); codes may be None
+        when every slot with frames is lost. The slot must have had its first chunk."""
         s = self._s
-        n = self._frames(codes)
+        n = None if codes is None else self._frames(codes)
         frames = _ints(frames, 'frames')
         n_max, any_first = s.check_frames(frames)
-        if n != n_max:
+        lost = check_lost(s.started, frames, lost, self._M)
+        if n is None:
+            if lost is None or any(f and not gone for f, gone in zip(frames, lost)):
+                raise ValueError('encx streaming: codes may be None only when every slot with frames is lost')
+        elif n != n_max:
             raise ValueError(f'encx streaming: {n} frames of codes for max(frames) = {n_max}')
+        if lost is not None and not s.plan.windows[0].P:
+            _refuse('concealment for a decoder whose first layer keeps no history (no held column to repeat)')
         if n_q is not None:
             check_rvq_shape(self.n_q, *self._embeds[0].shape)
-            n_q = check_n_q(frames, n_q, self.n_q)
-        if not codes.is_cuda:
+            n_q = check_n_q([0 if gone else f for f, gone in zip(frames, lost)] if lost else frames, n_q, self.n_q)
+        if codes is not None and not codes.is_cuda:
             raise RuntimeError('encx streaming takes device tensors (no CPU fallback)')
         s.put_slots(frames)
+        # the concealed step: its own graphs, taken only while a slot is lost or below full level
+        conceal = lost is not None or any(p < self._M for p in self._p)
+        if conceal:
+            self._put_conceal(lost or [False] * s.B)
         if n_q is not None:
             s.put_nq(n_q)
-            self._code_buf_nq(n).copy_(codes)
-            return s._step_slots(frames, n_max, any_first, self._body_nq, s._nq_graphs)[0]
-        buf = self._code_buf(n)
-        # clamped as in decode(); past a slot's count whatever the caller left becomes code 0
-        buf.copy_(torch.where(s.keep(n, 1).squeeze(1), codes.permute(1, 0, 2).clamp(0, self.bins - 1), 0))
-        return s._step_slots(frames, n_max, any_first, self._body_slots)[0]
+            buf = self._code_buf_nq(n_max)
+            buf.zero_() if codes is None else buf.copy_(codes)
+            if conceal:
+                out = s._step_slots(frames, n_max, any_first, self._body_conceal, self._conceal_graphs, (True,))[0]
+            else:
+                out = s._step_slots(frames, n_max, any_first, self._body_nq, s._nq_graphs)[0]
+            self._advance(frames, lost)
+            return out
+        buf = self._code_buf(n_max)
+        if codes is None:
+            buf.zero_()
+        else:
+            # clamped as in decode(); past a slot's count whatever the caller left becomes code 0
+            buf.copy_(torch.where(s.keep(n_max, 1).squeeze(1), codes.permute(1, 0, 2).clamp(0, self.bins - 1), 0))
+        if conceal:
+            out = s._step_slots(frames, n_max, any_first, self._body_conceal, self._conceal_graphs, (False,))[0]
+        else:
+            out = s._step_slots(frames, n_max, any_first, self._body_slots)[0]
+        self._advance(frames, lost)
+        return out
 
 
 # ---------------------------------------------------------------------------- packets
 MAX_PACKET_FRAMES = 255  # the header byte (include/encx.h: the packet format)
+
+
+def packet_frames(packet: bytes) -> int:
+    """The frame count a packet announces (header byte 0 of every packet form), 0 for b''. For a
+    packet that is held but cannot be decoded (StreamUnpacker.lose): the frames to conceal."""
+    return int(packet[0]) if len(packet) else 0
 
 
 def packet_bytes(n: int, K: int, bits: int) -> int:
@@ -994,15 +1219,18 @@ class _Packets:
             self._lm = lm_session(lm if lm is not None else model.get_lm_model(), self.B, self.n_q,
                                   self.max_frames, graphs, lm_format=self.lm_format)
         self._dev = None
+        self._lost: tp.Set[int] = set()  # StreamUnpacker.lose: slots whose packets are dropped unread
 
     def reset(self):
         """Every slot starts a new stream with its next packet (the raw form carries no state)."""
+        self._lost.clear()
         if self._lm is not None:
             self._lm.reset()
 
     def restart(self, slots):
         """As StreamEncoder.restart: the named slots' next packet begins a stream."""
         slots = check_restart(slots, self.B)
+        self._lost.difference_update(slots)
         if self._lm is not None:
             self._lm.restart(slots)
 
@@ -1117,6 +1345,31 @@ class StreamUnpacker(_Packets):
     def failed(self) -> tp.List[int]:
         return sorted(self._lm.failed) if self._lm is not None else []
 
+    def lose(self, slots):
+        """A packet of each named slot did not arrive. With use_lm=True the slot's LM context no
+        longer matches the sender's, so the slot joins `failed`, and until restart([b]) its
+        packets are dropped unread: they come back with 0 frames and zero codes, the other slots
+        decode, and nothing is decoded under a context the sender does not share (packet_frames
+        tells how many frames to conceal for such a packet). A raw packet carries no state:
+        without an LM this only checks the indices. Recovery: packer.restart([b]) and
+        unpacker.restart([b]) once the sender knows, which restarts the LM context only; the
+        encoder and the decoder go on (module docstring)."""
+        slots = check_restart(slots, self.B)
+        if self._lm is not None:
+            self._lost.update(slots)
+            self._lm.lose(slots)
+
+    def _drop_lost(self, packets):
+        """The packets with those of the lost slots replaced by b'' (unread), or None when that
+        leaves no packet at all."""
+        if not self._lost or len(packets) != self.B:
+            return packets
+        kept = [b'' if b in self._lost else p for b, p in enumerate(packets)]
+        if any(len(p) for p in packets if isinstance(p, (bytes, bytearray))) and \
+                not any(len(p) for p in kept if isinstance(p, (bytes, bytearray))):
+            return None
+        return kept
+
     def _headers(self, packets):
         if len(packets) != self.B:
             raise ValueError(f'encx streaming: packets for {len(packets)} slots, the session has {self.B}')
@@ -1179,6 +1432,10 @@ class StreamUnpacker(_Packets):
         """slot_n_q=True: -> (codes [B, n_q, max(frames)], frames, n_q) from variable-bandwidth
         packets, n_q[b] = 0 for an empty packet and zero rows at k >= n_q[b]: ready for
         StreamDecoder.decode_slots(codes, frames, n_q)."""
+        packets = self._drop_lost(packets)
+        if packets is None:  # every packet of the step belongs to a lost slot: nothing to decode
+            codes = torch.zeros(self.B, self.n_q, 0, dtype=torch.int64, device=next(self.model.parameters()).device)
+            return (codes, [0] * self.B, [0] * self.B) if self.lm_format == 2 else (codes, [0] * self.B)
         if self.lm_format == 2:
             frames, n_q = self._headers_nq(packets)
             codes, failed = self._lm.decode_slots([bytes(p[2:]) for p in packets], frames, n_q)

@@ -919,6 +919,50 @@ int encx_bitunpack_slots_nq(const uint8_t* in, int64_t in_stride, int64_t B, int
                             const int32_t* slots, const int32_t* nq, int64_t* codes, int64_t s_b, int64_t s_k,
                             int64_t s_t, encx_stream_t stream);
 
+/* ------------------------------------------- concealing a lost packet, per slot (encx/streaming.py)
+ * A slot whose packet did not arrive decodes its LAST LATENT FRAME again for the `count` frames of the
+ * step: after the end-of-step roll, column P-1 of the decoder's first window (P: that window's
+ * history) is the last latent frame the slot decoded, and a slot that sits out keeps it. Everything
+ * behind the first window runs as in any step, so the slot's carried state advances by count frames.
+ * The slot's output fades under two integers per slot, p (0..M, M = fade_frames * recover_frames *
+ * hop <= 2^24: full level) and r (the samples concealed in the current loss run). Per output sample:
+ *   concealed step   r += 1; if r > hold_frames * hop then p = max(0, p - recover_frames)
+ *   delivered step   p = min(M, p + fade_frames)          (and r = 0 at the end of the step)
+ * and the sample is written as x where p == M, else x * ((float)p * invM) with invM = 1.0f / (float)M
+ * (p is the value after the sample's update). The kernels evaluate this in closed form per sample.
+ *
+ * A third device table beside slots[2B] and nq[B], int32 conceal[B][4]:
+ *   word 0   lost: non-zero when the slot's step is concealed
+ *   word 1   p at the START of the step (clamped to 0..M by the kernel)
+ *   word 2   r at the START of the step (negative values read as 0)
+ *   word 3   0
+ * The host advances p and r itself (they depend only on arguments it sees) and uploads the table
+ * when it changed. B 1..64, n_max 1..255, P 1..64; anything else, or a NULL pointer, is ENCX_EINVAL
+ * before any launch. No kernel forms an address from a column a slot does not own.
+ *
+ * encx_stream_rvq_decode_slots_conceal: encx_stream_rvq_decode_slots with the table. Columns t <
+ * count of a lost slot are out[b*o_b + d*o_d + t*o_t] = held[b*o_b + d*o_d] (held: column P-1 of the
+ * window `out` points into, the same b and d strides); the slot's codes and nq[b] are not read. The
+ * other slots, and columns t >= count, are bit for bit as without the table. One launch for all slots.
+ * encx_stream_conceal_fill: the same after the per-layer dequantizer (encx_rvq_gather + copy): win
+ * [b*w_b + d*w_d + column] is the first window from its column 0; rows of lost slots get columns
+ * [P, P + count) <- column P-1. w_d >= P + n_max, w_b >= D * w_d. One launch, a row per wave.
+ * encx_stream_conceal_out: the step's output. x[b*x_b + c*x_c + j] is the decoder's last window,
+ * read in place for j < count*hop only; out [B][C][n_max*hop] contiguous gets 0 for j >= count*hop
+ * and the faded sample elsewhere. hold_frames 0..255, fade_frames and recover_frames 1..255, M <=
+ * 2^24, x_c >= n_max*hop, x_b >= C*x_c. 16-byte loads and stores when hop, x_b and x_c are multiples
+ * of 4 and both pointers are 16-byte aligned, dwords otherwise; the bits do not depend on the route. */
+int encx_stream_rvq_decode_slots_conceal(const int64_t* codes, int64_t c_b, int64_t c_k, int64_t c_t,
+                                         const float* packed, int64_t B, int64_t K_max, int64_t bins, int64_t D,
+                                         int64_t n_max, const int32_t* slots, const int32_t* nq,
+                                         const int32_t* conceal, const float* held, float* out, int64_t o_b,
+                                         int64_t o_d, int64_t o_t, encx_stream_t stream);
+int encx_stream_conceal_fill(float* win, int64_t w_b, int64_t w_d, int64_t B, int64_t D, int64_t P, int64_t n_max,
+                             const int32_t* slots, const int32_t* conceal, encx_stream_t stream);
+int encx_stream_conceal_out(const float* x, int64_t x_b, int64_t x_c, float* out, int64_t B, int64_t C, int64_t hop,
+                            int64_t n_max, const int32_t* slots, const int32_t* conceal, int64_t hold_frames,
+                            int64_t fade_frames, int64_t recover_frames, encx_stream_t stream);
+
 /* The LM over slots. Device state per slot: pos[b] (int64, frames coded so far) and prev[b][K]
  * (int64, the LM input index of the slot's next row: 1 + its last code, 0 at the start of a
  * stream); on a first chunk the kernels take both as 0 themselves, so a restart costs no launch.

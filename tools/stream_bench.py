@@ -21,8 +21,12 @@ python tools/stream_bench.py [--batches 1,16,64] [--frames 1,4] [--rounds 5] [--
 --nq measures a bandwidth (n_q) per slot (nq_section: the fused quantizer against the step without
 n_q) and writes profiles/stream/stream_bench_nq.json.
 
+--conceal measures loss concealment (conceal_section: decode_slots with lost slots against the
+same session's loss-free step) and writes profiles/stream/stream_bench_conceal.json.
+
 python tools/stream_bench.py --slots [--rounds 5] [--slots-out FILE]
 python tools/stream_bench.py --nq [--rounds 5] [--nq-out FILE]
+python tools/stream_bench.py --conceal [--rounds 5] [--conceal-out FILE]
 """
 import argparse
 import json
@@ -161,8 +165,59 @@ def nq_section(args, torch, m, dev, hop, timed, B=64):
                       'alternating round by round, after warm-up', 'rows': rows}
 
 
+def conceal_section(args, torch, m, dev, hop, timed, B=64, K=8):
+    """Loss concealment at B = 64 (graph replay), n = 1 and 4 frames per step, on the per-layer
+    dequantizer (decode_slots without n_q) and on the fused one (with n_q): the decode step with
+    none, one in eight and all of the slots lost, one session per (path, n). `none` is the
+    session's loss-free decode_slots step, the step every session ran before; the cases alternate
+    round by round, and each block is preceded by two untimed steps, so that the fade back to full
+    level after a block of losses (one frame with the default conceal_recover) is not in it."""
+    from encx.streaming import StreamDecoder
+    shares = {'none': [False] * B, 'eighth': [b % 8 == 0 for b in range(B)], 'all': [True] * B}
+    rows = []
+    for path in ('layers', 'fused'):
+        for n in (1, 4):
+            g = torch.Generator().manual_seed(7000 + n)
+            dec = StreamDecoder(m, B, K)
+            mf, frames, nq = [dec.min_first_frames] * B, [n] * B, [K] * B
+            kw = {'n_q': nq} if path == 'fused' else {}
+            dec.decode_slots(torch.randint(0, 1024, (B, K, mf[0]), generator=g).to(dev), mf, **kw)
+            codes = torch.randint(0, 1024, (B, K, n), generator=g).to(dev)
+            fns = {k: (lambda lost=lost: dec.decode_slots(codes, frames, lost=lost, **kw)) for k, lost in shares.items()}
+
+            def block(fn, iters):
+                fn()
+                fn()
+                torch.cuda.synchronize()
+                return timed(fn, iters)
+
+            iters = {k: max(5, int(args.min_seconds * 1e3 / args.rounds / max(block(fn, 5), 1e-3)) + 1)
+                     for k, fn in fns.items()}
+            ms = {k: [] for k in fns}
+            for _ in range(args.rounds):
+                for k, fn in fns.items():
+                    ms[k].append(block(fn, iters[k]))
+            row = {'path': path, 'n': n}
+            row.update({k: stats(v) for k, v in ms.items()})
+            for k in ('eighth', 'all'):
+                row[f'{k}_over_none'] = round(row[k]['ms'] / row['none']['ms'], 4)
+            row['none_spread'] = round((row['none']['max'] - row['none']['min']) / row['none']['ms'], 4)
+            row['conceal_graphs'] = len(dec._conceal_graphs)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return {'metric': f'ms per decode_slots step at B = {B} (graph replay), n_q {K}: none / one in eight / all of '
+                      'the slots lost; none is the loss-free step of the same session',
+            'device': torch.cuda.get_device_name(0), 'model': 'causal 24 kHz SEANet, random weights',
+            'rounds': args.rounds,
+            'timing': f'device events around blocks of steps, >= {args.min_seconds} s per case, the cases '
+                      'alternating round by round, two untimed steps before each block', 'rows': rows}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--conceal', action='store_true', help='only the loss concealment section (B = 64)')
+    ap.add_argument('--conceal-out', type=str,
+                    default=os.path.join(ROOT, 'profiles', 'stream', 'stream_bench_conceal.json'))
     ap.add_argument('--nq', action='store_true', help='only the per-slot bandwidth section (B = 64)')
     ap.add_argument('--nq-out', type=str, default=os.path.join(ROOT, 'profiles', 'stream', 'stream_bench_nq.json'))
     ap.add_argument('--slots', action='store_true', help='only the per-slot section (B = 64)')
@@ -207,6 +262,15 @@ def main():
         torch.cuda.synchronize()
         iters = max(5, int(args.min_seconds * 1e3 / args.rounds / max(timed(fn, 5), 1e-3)) + 1)
         return stats([timed(fn, iters) for _ in range(args.rounds)]), iters
+
+    if args.conceal:
+        with torch.no_grad():
+            res = conceal_section(args, torch, m, dev, hop, timed)
+        if args.conceal_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.conceal_out)), exist_ok=True)
+            with open(args.conceal_out, 'w') as f:
+                f.write(json.dumps(res, indent=1) + '\n')
+        return
 
     if args.nq:
         with torch.no_grad():
