@@ -342,8 +342,11 @@ class Conv1dFn(torch.autograd.Function):
         if role == 'tail' and has_res:
             # skip gradient of an identity-shortcut residual block: the head conv of the same
             # block adds its bwd-data result into this buffer (accumulate=1), so autograd sees
-            # no second path into the block input and launches no elementwise add
-            link.grad, dres = dy, None
+            # no second path into the block input and launches no elementwise add. A copy: dy is
+            # autograd's (or the caller's own tensor, a retained grad, a hook's argument) and
+            # must not be written; the copy costs what the add it replaces cost, and the
+            # conv-shortcut blocks of the EnCodec configs never take this path
+            link.grad, dres = dy.clone(), None
         return dx, dv, dg, db, dres, None, None, None, None, None, None, None, None
 
 

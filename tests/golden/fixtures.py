@@ -41,6 +41,40 @@ def cfg48k(**kw):
                   segment=kw.pop('segment', 0.1), **kw)
 
 
+# The g14 fixture's SEANet architectures (everything the default model does not use): the Config
+# arguments, the seed of the synthetic state and the time steps per hop-sized frame of the CPU run.
+# A is also a streamable EncodecModel (dimension 128: the g1 codebooks serve; 80 kbps at its
+# 4000 frames/s is n_q 2).
+ARCHS = {
+    'A': dict(seed=141, channels=1, causal=True, norm='weight_norm', n_filters=16, ratios=(3, 2),
+              n_residual_layers=3, true_skip=False, compress=2, kernel_size=7, last_kernel_size=7,
+              residual_kernel_size=3, lstm=1, dimension=128),
+    'B': dict(seed=142, channels=2, causal=True, norm='weight_norm', n_filters=12, ratios=(6, 4),
+              n_residual_layers=2, true_skip=True, compress=4, kernel_size=5, last_kernel_size=3,
+              residual_kernel_size=5, lstm=3, dimension=40),
+    'C': dict(seed=143, channels=1, causal=False, norm='time_group_norm', n_filters=8, ratios=(5, 3),
+              n_residual_layers=2, true_skip=False, compress=2, kernel_size=7, last_kernel_size=7,
+              residual_kernel_size=3, lstm=0, dimension=64),
+}
+
+
+def arch_cfg(name):
+    """-> (oracle Config, seed of its synthetic state) of g14's architecture `name`."""
+    from oracle.encodec_oracle import Config
+    kw = dict(ARCHS[name])
+    seed = kw.pop('seed')
+    return Config(audio_normalize=False, target_bandwidths=(80.,), n_q=2, **kw), seed
+
+
+def arch_modules(name, mods):
+    """SEANetEncoder / SEANetDecoder of architecture `name` from `mods` (encx.modules here, the
+    reference's modules in make_goldens.py: the constructors take the same arguments)."""
+    kw = dict(ARCHS[name])
+    kw.pop('seed')
+    kw['ratios'] = list(kw['ratios'])
+    return mods.SEANetEncoder(**kw), mods.SEANetDecoder(**kw)
+
+
 def codebooks_from_stats(stats, seed, n_used, n_total):
     """Same draws as make_goldens.fill_codebooks."""
     cbs = synth_codebooks(stats, seed)
@@ -105,7 +139,8 @@ def g13_samples(n, count=64):
     return np.unique(np.linspace(0, n - 1, min(n, count)).round().astype(np.int64))
 
 
-__all__ = ['load', 'g13_samples', 'T', 'model_state', 'disc_state', 'cfg48k', 'codebooks_from_stats', 'g3_codebooks',
+__all__ = ['load', 'g13_samples', 'T', 'model_state', 'disc_state', 'cfg48k', 'arch_cfg', 'arch_modules', 'ARCHS',
+           'codebooks_from_stats', 'g3_codebooks',
            'certified', 'rvq_certified', 'synth_wave', 'rng']
 
 

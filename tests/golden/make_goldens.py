@@ -23,6 +23,9 @@ Fixture map:
   g9_step48k.npz   config-5 analogue: 48 kHz stereo, non-causal, time_group_norm, segment 0.1 s
                    (two frames: 4800 + 48 samples, linear overlap-add), gen-only and GAN steps
   g13_ddp.npz      the reference's train_one_step under DDP, 2 ranks over gloo (G13 below)
+  g14_seanet_arch.npz  SEANetEncoder -> SEANetDecoder of three non-default architectures
+                   (fixtures.ARCHS: n_residual_layers 2-3 with dilations, true_skip, compress 4,
+                   other kernel sizes / ratios / widths, lstm 0 / 1 / 3), forward + all grads
 """
 import os
 import sys
@@ -853,8 +856,45 @@ def g13():
     save('g13_ddp.npz', **out)
 
 
+# ------------------------------------------------------------------------------------ G14
+G14_B, G14_HOPS = 2, 60
+
+
+def g14():
+    """The reference's SEANetEncoder -> SEANetDecoder (no quantizer) for fixtures.ARCHS, loaded
+    with synth_state(model_param_shapes(cfg)): the oracle's parameter names and shapes must be
+    the reference's state dict exactly. Parameter grads as (sum, abs-sum); dx in full."""
+    from fixtures import arch_cfg, arch_modules, ARCHS
+    from oracle.encodec_oracle import model_param_shapes
+    out = {}
+    for i, name in enumerate(sorted(ARCHS)):
+        cfg, seed = arch_cfg(name)
+        enc, dec = arch_modules(name, R.modules)
+        mods = {'encoder': enc, 'decoder': dec}
+        shapes = model_param_shapes(cfg)
+        sd = {f'{k}.{n}': v for k, m in mods.items() for n, v in m.state_dict().items()}
+        assert set(sd) == set(shapes), set(sd) ^ set(shapes)
+        assert all(tuple(sd[k].shape) == tuple(v) for k, v in shapes.items())
+        st = synth_state(shapes, seed)
+        for k, m in mods.items():
+            m.load_state_dict({n[len(k) + 1:]: t(v) for n, v in st.items() if n.startswith(k + '.')})
+        hop = int(np.prod(cfg.ratios))
+        x = t(synth_wave((G14_B, cfg.channels, G14_HOPS * hop), 1400 + i)).requires_grad_(True)
+        emb = enc(x)
+        y = dec(emb)
+        gy = t(synth_wave(tuple(y.shape), 1410 + i, amp=1.0))
+        y.backward(gy)
+        out.update({f'{name}/x': x.detach().numpy(), f'{name}/gy': gy.numpy(), f'{name}/emb': emb.detach().numpy(),
+                    f'{name}/y': y.detach().numpy(), f'{name}/dx': x.grad.numpy()})
+        for k, m in mods.items():
+            for n, v in m.named_parameters():
+                g = v.grad.double()
+                out[f'{name}/g/{k}.{n}'] = np.array([g.sum().item(), g.abs().sum().item()])
+    save('g14_seanet_arch.npz', **out)
+
+
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['g1', 'g2', 'g3', 'g4', 'g5', 'g6', 'g7', 'g8', 'g9', 'g10', 'g11', 'g12', 'g13']
+    which = sys.argv[1:] or ['g1', 'g2', 'g3', 'g4', 'g5', 'g6', 'g7', 'g8', 'g9', 'g10', 'g11', 'g12', 'g13', 'g14']
     for w in which:
         torch.manual_seed(0)
         globals()[w]()

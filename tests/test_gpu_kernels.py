@@ -94,6 +94,10 @@ MODEL_LAYERS = [
     ('conv', 256, 256, 1, 1, True, 600), ('conv', 128, 256, 1, 1, False, 600),
     ('conv', 64, 128, 1, 1, True, 3000), ('conv', 128, 128, 1, 1, True, 1000),
     ('conv', 128, 128, 1, 1, True, 3000),  # the 1x1 GEMM past PW_TMAX (>= 128-channel reduction)
+    # strides other than 2, 4, 5, 8 (`ratios` is a constructor argument): K = 2r for r = 3, 6, 7, the
+    # routes keyed on K and stride (the polyphase J, the short-T im2col GEMM, pw_ok), an odd T
+    ('conv', 24, 48, 6, 3, True, 600), ('conv', 48, 96, 12, 6, True, 96), ('conv', 32, 64, 14, 7, True, 2401),
+    ('convtr', 48, 24, 6, 3, True, 200), ('convtr', 96, 48, 12, 6, True, 16), ('convtr', 64, 32, 14, 7, True, 343),
 ]
 
 

@@ -68,9 +68,9 @@ def stream_encode(m, x, schedule, graphs=True, max_frames=8, enc=None):
     from encx.streaming import StreamEncoder
     enc = enc or StreamEncoder(m, x.shape[0], max_frames=max_frames, graphs=graphs)
     assert sum(schedule) * enc.hop_length == x.shape[-1]
-    embs, codes, off = [], [], 0
+    embs, codes, off, hop = [], [], 0, enc.hop_length
     for n in schedule:
-        c, e = enc.encode(x[:, :, off * HOP:(off + n) * HOP].to(DEV), return_latent=True)
+        c, e = enc.encode(x[:, :, off * hop:(off + n) * hop].to(DEV), return_latent=True)
         assert c.shape == (x.shape[0], enc.n_q, n) and c.dtype == torch.int64
         embs.append(e)
         codes.append(c)
@@ -84,7 +84,7 @@ def stream_decode(m, codes, schedule, graphs=True, max_frames=8, dec=None):
     ys, off = [], 0
     for n in schedule:
         y = dec.decode(codes[:, :, off:off + n].to(DEV))
-        assert y.shape == (codes.shape[0], m.channels, n * HOP)
+        assert y.shape == (codes.shape[0], m.channels, n * dec.hop_length)
         ys.append(y)
         off += n
     return torch.cat(ys, 2), dec

@@ -296,6 +296,57 @@ def test_oracle_train_step_fixture(gan):
                                        d['gan/d/' + k], rtol=2e-4, atol=2e-5)
 
 
+# --------------------------------------------------------------------------- G14 SEANet architectures
+@pytest.mark.parametrize('name', ['A', 'B', 'C'])
+def test_oracle_seanet_arch_fixture(name):
+    """The full SEANet constructor (modules/seanet.py:39-63, 91-144, 174-238) -- n_residual_layers
+    with dilation_base ** j, true_skip, compress, the three kernel sizes, n_filters, dimension,
+    lstm 0 / 1 / 3 -- against the reference's encoder -> decoder on fixtures.ARCHS. The state is
+    synthesised from the oracle's own model_param_shapes, which g14 asserted to be the reference's
+    state dict. Tolerances are the default plan's: the latent as G1's latent, the wave as G1's
+    wave (and the input grad, the other tensor that crosses the whole stack, as the wave), the
+    parameter grads' (sum, abs-sum) as G7's parameter sums."""
+    from fixtures import arch_cfg
+    d = load('g14_seanet_arch.npz')
+    cfg, seed = arch_cfg(name)
+    p = {k: v.clone().requires_grad_(True) for k, v in model_state(cfg, seed).items()}
+    x = T(d[f'{name}/x']).clone().requires_grad_(True)
+    assert x.shape == (2, cfg.channels, 60 * int(np.prod(cfg.ratios)))
+    emb = O.run_plan(x, p, cfg.enc_plan, cfg.causal, cfg.norm)
+    y = O.run_plan(emb, p, cfg.dec_plan, cfg.causal, cfg.norm)
+    assert emb.shape == (2, cfg.dimension, 60)
+    close(emb, d[f'{name}/emb'], rtol=1e-4, atol=1e-6)
+    close(y, d[f'{name}/y'], rtol=1e-3, atol=1e-6)
+    y.backward(T(d[f'{name}/gy']))
+    close(x.grad, d[f'{name}/dx'], rtol=1e-3, atol=1e-6)
+    keys = [k[len(name) + 3:] for k in d.files if k.startswith(f'{name}/g/')]
+    assert set(keys) == set(p)
+    for k, v in p.items():
+        g = v.grad.double()
+        np.testing.assert_allclose([g.sum().item(), g.abs().sum().item()], d[f'{name}/g/{k}'],
+                                   rtol=2e-4, atol=2e-5, err_msg=k)
+
+
+def test_seanet_plan_defaults_are_the_old_plan():
+    """The default arguments give the plan this oracle always had: 5-tuple residual blocks at the
+    reference's nn.Sequential indices; other architectures move the indices as nn.Sequential does."""
+    enc, dec = O.seanet_plan()
+    assert [L for L in enc if L[0] == 'res'] == [('res', f'encoder.model.{i}', c, 3, 2)
+                                                 for i, c in ((1, 32), (4, 64), (7, 128), (10, 256))]
+    assert [L[1] for L in enc] == [f'encoder.model.{i}' for i in (0, 1, 3, 4, 6, 7, 9, 10, 12, 13, 15)]
+    assert [L[1] for L in dec] == [f'decoder.model.{i}' for i in (0, 1, 3, 4, 6, 7, 9, 10, 12, 13, 15)]
+    enc, dec = O.seanet_plan(n_filters=16, ratios=(3, 2), n_residual_layers=3, lstm=1)
+    assert [(L[0], L[1][14:]) + tuple(L[5:]) for L in enc if L[0] == 'res'] == [
+        ('res', '1'), ('res', '2', 2, False), ('res', '3', 4, False),
+        ('res', '6'), ('res', '7', 2, False), ('res', '8', 4, False)]
+    assert [L[1] for L in enc if L[0] != 'res'] == [f'encoder.model.{i}' for i in (0, 5, 10, 11, 13)]
+    assert [L[1] for L in dec] == [f'decoder.model.{i}' for i in (0, 1, 3, 4, 5, 6, 8, 9, 10, 11, 13)]
+    enc, dec = O.seanet_plan(lstm=0, true_skip=True)
+    assert all(L[0] != 'lstm' for L in enc + dec) and enc[-1][1] == 'encoder.model.14'
+    assert enc[1] == ('res', 'encoder.model.1', 32, 3, 2, 1, True)
+    assert not any('shortcut' in k for k in O.model_param_shapes(O.Config(true_skip=True)))
+
+
 # --------------------------------------------------------------------------- G9 48 kHz stereo
 @pytest.mark.parametrize('gan', [False, True])
 def test_oracle_train_step_48k_fixture(gan):

@@ -79,6 +79,69 @@ def test_refusals_fire_on_a_cpu_model():
     _refused(m)
 
 
+def arch_model(name, **over):
+    """fixtures.ARCHS[name] as an EncodecModel (two codebooks, no normalisation, no segments)."""
+    import fixtures
+    import encx.modules as M
+    from encx.quantization import ResidualVectorQuantizer
+    kw = {k: v for k, v in fixtures.ARCHS[name].items() if k != 'seed'}
+    kw.update(over, ratios=list(kw['ratios']))
+    enc, dec = M.SEANetEncoder(**kw), M.SEANetDecoder(**kw)
+    m = EncodecModel(enc, dec, ResidualVectorQuantizer(dimension=kw['dimension'], n_q=2, bins=1024), [80.], 24000,
+                     kw['channels'], normalize=False, segment=None)
+    m.set_target_bandwidth(80.)
+    return m.eval()
+
+
+def test_layer_plan_of_a_dilated_three_block_model():
+    """Arch A: ratios (3, 2), three blocks per stage with dilations 1, 2, 4, one LSTM layer."""
+    from encx import streaming as S
+    m = arch_model('A')
+    enc, dec = S.encoder_plan(m), S.decoder_plan(m)
+    for plan in (enc, dec):
+        for L in plan.layers:
+            if L.kind == 'conv':
+                assert L.P == (L.K - 1) * L.dilation - (L.stride - 1), L.name
+                assert plan.windows[L.src].P >= L.P
+        k3 = [L for L in plan.layers if L.kind == 'conv' and L.K == 3]
+        assert [L.dilation for L in k3] == [1, 2, 4] * 2
+        # each dilated conv is the only consumer with a history of its block's input window
+        assert [plan.windows[L.src].P for L in k3] == [2, 4, 8] * 2
+        assert {L.module.lstm.num_layers for L in plan.layers if L.kind == 'lstm'} == {1}
+    rates = lambda plan: [plan.windows[L.src].rate for L in plan.layers if L.kind == 'conv' and L.K == 3]
+    assert rates(enc) == [6] * 3 + [3] * 3 and rates(dec) == [3] * 3 + [6] * 3
+    assert [(L.K, L.stride, L.P) for L in enc.layers if L.kind == 'conv' and L.stride > 1] == [(4, 2, 2), (6, 3, 3)]
+    assert [(L.K, L.stride) for L in dec.layers if L.kind == 'convtr'] == [(6, 3), (4, 2)]
+    assert sorted({w.rate for w in enc.windows}) == sorted({w.rate for w in dec.windows}) == [1, 3, 6]
+    assert (enc.windows[0].rate, enc.windows[enc.layers[-1].dst].rate) == (6, 1)
+    assert (dec.windows[0].rate, dec.windows[dec.layers[-1].dst].rate) == (1, 6)
+    assert enc.hop_length == dec.hop_length == 6
+    # the smallest first chunk, from the plan's windows: every reflect-filled history of P columns
+    # needs more than P columns, at `rate` columns per frame
+    for plan in (enc, dec):
+        want = max(w.P // w.rate + 1 for w in plan.windows if w.P and w.fill == 'reflect')
+        assert plan.min_first_frames == want == 7  # the K = 7 conv at one column per frame
+
+
+def test_identity_shortcut_is_refused_by_name():
+    from encx import streaming as S
+    m = arch_model('B')
+    with pytest.raises(NotImplementedError, match=r'identity shortcut \(true_skip=True\)'):
+        S.StreamEncoder(m, 1)
+    with pytest.raises(NotImplementedError, match=r'identity shortcut \(true_skip=True\)'):
+        S.StreamDecoder(m, 1, 2)
+
+
+@pytest.mark.parametrize('lstm', [0, 3])
+def test_plans_build_without_an_lstm_and_with_three_layers(lstm):
+    from encx import streaming as S
+    m = arch_model('A', lstm=lstm)
+    for plan in (S.encoder_plan(m), S.decoder_plan(m)):
+        ls = [L for L in plan.layers if L.kind == 'lstm']
+        assert len(ls) == (1 if lstm else 0) and all(L.module.lstm.num_layers == lstm for L in ls)
+        assert plan.hop_length == 6 and plan.min_first_frames == 7
+
+
 def test_supported_cpu_model_has_no_cpu_fallback():
     from encx import streaming as S
     with pytest.raises(RuntimeError, match='no CPU fallback'):
