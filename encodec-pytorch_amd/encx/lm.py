@@ -34,6 +34,7 @@ from torch import nn
 
 from ._lib import call, lib, stream, ensure_device, ENCX_AC_POS
 from .ac import new_decoder_state
+from .slots import DeviceTable, _ints, check_frames, check_n_q, check_restart
 
 TOTAL_RANGE_BITS = 24   # ArithmeticCoder default (ac.py:96), as compress.py uses it
 ROUNDOFF = 1e-8         # build_stable_quantized_cdf defaults (ac.py:18-20)
@@ -512,8 +513,6 @@ class _LMSlots:
         self.started = [False] * self.B
         self.failed: tp.Set[int] = set()
         self._ready = False
-        self._tab = None  # the slot table as last uploaded
-        self._nq_tab = None  # lm_format 2: the nq table as last uploaded
         self._graphs: tp.Dict[int, tp.Any] = {}
 
     def reset(self):
@@ -525,13 +524,11 @@ class _LMSlots:
         """The named slots start a new stream with their next packet: the LM's position and
         context are taken as empty by the kernels on that packet (the slot table's first-chunk
         flag), so this launches nothing and disturbs no other slot."""
-        from .streaming import check_restart
         for b in check_restart(slots, self.B):
             self.started[b] = False
             self.failed.discard(b)
 
     def _check_frames(self, frames):
-        from .streaming import check_frames, _ints
         frames = _ints(frames, 'frames')
         n_max, _ = check_frames(self.started, frames, 1, self.max_frames)
         for b, f in enumerate(frames):
@@ -540,8 +537,7 @@ class _LMSlots:
         return frames, n_max
 
     def _check_n_q(self, frames, n_q):
-        """n_q goes with lm_format=2 and only with it -> the nq table (streaming.check_n_q), or None."""
-        from .streaming import check_n_q
+        """n_q goes with lm_format=2 and only with it -> the nq table (slots.check_n_q), or None."""
         if (self.lm_format == 2) != (n_q is not None):
             raise ValueError('encx LM streaming: n_q goes with lm_format=2, and only with it')
         return check_n_q(frames, n_q, self.K) if n_q is not None else None
@@ -558,21 +554,16 @@ class _LMSlots:
         self._kv = [torch.zeros(B, self.R, 2 * lm.dim, device=dev) for _ in tr.layers]
         self._pos = torch.zeros(B, dtype=torch.int64, device=dev)
         self._prev = torch.zeros(B, K, dtype=torch.int64, device=dev)
-        self._slots = torch.zeros(B, 2, dtype=torch.int32, device=dev)
-        self._nq = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._slots = DeviceTable(B, 2, dev)
+        self._nq = DeviceTable(B, 1, dev)  # lm_format 2
         self._cols = torch.arange(self.max_frames, device=dev, dtype=torch.int32)
         self._ready = True
 
-    def _put_slots(self, frames):
-        tab = [(int(f), int(f > 0 and not on)) for f, on in zip(frames, self.started)]
-        if tab != self._tab:  # a sustained step repeats its table: no upload
-            self._slots.copy_(torch.tensor(tab, dtype=torch.int32))
-            self._tab = tab
-
-    def _put_nq(self, n_q):
-        if n_q is not None and n_q != self._nq_tab:  # uploaded only when it changed
-            self._nq.copy_(torch.tensor(n_q, dtype=torch.int32))
-            self._nq_tab = list(n_q)
+    def _put(self, frames, n_q):
+        """This step's tables; a sustained step repeats them: no upload."""
+        self._slots.put([(int(f), int(f > 0 and not on)) for f, on in zip(frames, self.started)])
+        if n_q is not None:
+            self._nq.put(n_q)
 
     def _rows(self, T, n_max, codes, dstep):
         """The LM input and every layer for T rows per slot under the slot table -> x [B*T][dim]."""
@@ -620,21 +611,17 @@ class _LMSlots:
         eagerly). The first step of a key runs the body once eagerly under an EMPTY table (every
         row dead: each kernel is loaded, no state moves), then captures it; the table is device
         memory, so the graph replays for any counts."""
-        if not self.graphs:
-            self._put_slots(frames)
-            self._put_nq(n_q)
-            return None
-        g = self._graphs.get(key)
-        if g is None:
-            self._slots.zero_()
-            self._tab = None
-            body(key)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):  # one stream: no parallel branches
+        g = None
+        if self.graphs:
+            g = self._graphs.get(key)
+            if g is None:
+                self._slots.clear()
                 body(key)
-            self._graphs[key] = g
-        self._put_slots(frames)
-        self._put_nq(n_q)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):  # one stream: no parallel branches
+                    body(key)
+                self._graphs[key] = g
+        self._put(frames, n_q)
         return g
 
 
@@ -715,7 +702,7 @@ class LMStreamEncoder(_LMSlots):
         b = self._buf(n_max)
         g = self._run(n_max, self._body, frames, n_q)
         # the graph's own input; past a slot's count whatever the caller left becomes code 0
-        keep = (self._cols[:n_max] < self._slots[:, :1]).unsqueeze(1)
+        keep = (self._cols[:n_max] < self._slots.t[:, :1]).unsqueeze(1)
         b['codes'].copy_(torch.where(keep, codes, 0))
         if g is not None:
             g.replay()
@@ -762,7 +749,6 @@ class LMStreamDecoder(_LMSlots):
     def lose(self, slots):
         """A packet of each named slot did not arrive: its context no longer matches the
         sender's, so the slot is failed, exactly as after a bad packet, until restart([b])."""
-        from .streaming import check_restart
         self.failed.update(check_restart(slots, self.B))
 
     def _ensure(self):

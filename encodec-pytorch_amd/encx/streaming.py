@@ -133,6 +133,8 @@ from torch import nn
 
 from . import ops
 from ._lib import call, stream, ensure_device
+from .lm import LMStreamEncoder, LMStreamDecoder
+from .slots import DeviceTable, _ints, check_frames, check_n_q, check_restart  # noqa: F401 (re-exported)
 from .modules.conv import SConv1d, SConvTranspose1d
 from .modules.lstm import SLSTM
 from .modules.seanet import SEANetEncoder, SEANetResnetBlock
@@ -297,60 +299,7 @@ def decoder_plan(model) -> Plan:
     return layer_plan(model.decoder, 1)
 
 
-# ---------------------------------------------------------------------------- per-slot validation
-def _ints(values, what):
-    try:
-        return [operator.index(v) for v in values]
-    except TypeError:
-        raise ValueError(f'encx streaming: {what} must be a sequence of ints') from None
-
-
-def check_frames(started: tp.Sequence[bool], frames, min_first_frames: int, max_frames: int):
-    """frames[b] = latent frames slot b delivers this step, checked against each slot's own state
-    (started[b]: it has had its first chunk). -> (n_max, any_first): the columns the step
-    computes and whether any slot is on its first chunk. Raises ValueError; host data only."""
-    frames = _ints(frames, 'frames')
-    if len(frames) != len(started):
-        raise ValueError(f'encx streaming: frames for {len(frames)} slots, the session has {len(started)}')
-    any_first = False
-    for b, (on, f) in enumerate(zip(started, frames)):
-        if not 0 <= f <= max_frames:
-            raise ValueError(f'encx streaming: a chunk of {f} frames in slot {b} (0..max_frames={max_frames})')
-        if f and not on:
-            if f < min_first_frames:
-                raise ValueError(f'encx streaming: the first chunk of slot {b} needs at least '
-                                 f'{min_first_frames} frames (got {f})')
-            any_first = True
-    if not any(frames):
-        raise ValueError('encx streaming: no slot delivers a frame')
-    return max(frames), any_first
-
-
-def check_n_q(frames, n_q, n_q_max: int) -> tp.List[int]:
-    """n_q[b] = the codebooks slot b uses this step: an int in 1..n_q_max for a slot that delivers
-    frames; whatever stands at a slot with 0 frames is ignored. -> the table the kernels read, with
-    0 at the slots that sit out. Raises ValueError; host data only."""
-    try:
-        n_q = list(n_q)
-    except TypeError:
-        raise ValueError('encx streaming: n_q must be a sequence of ints') from None
-    if len(n_q) != len(frames):
-        raise ValueError(f'encx streaming: n_q for {len(n_q)} slots, the step has {len(frames)}')
-    out = []
-    for b, (f, q) in enumerate(zip(frames, n_q)):
-        if not f:
-            out.append(0)
-            continue
-        try:
-            q = operator.index(q)
-        except TypeError:
-            raise ValueError(f'encx streaming: n_q of slot {b} is not an int') from None
-        if not 1 <= q <= n_q_max:
-            raise ValueError(f'encx streaming: n_q {q} in slot {b} (1..{n_q_max})')
-        out.append(q)
-    return out
-
-
+# ---------------------------------------------------------------------------- concealment, the host side
 MAX_FADE = 1 << 24  # the fade position is multiplied as an fp32: exact up to 2^24
 _R_CAP = 1 << 30    # r saturates here: past the hold only r > hold is ever asked of it
 
@@ -427,15 +376,6 @@ def fade_gains(positions, M: int):
     return positions.astype(np.float32) * (np.float32(1) / np.float32(M))
 
 
-def check_restart(slots, batch: int) -> tp.List[int]:
-    """The slot indices of a restart(), each in 0..batch-1 (ValueError otherwise)."""
-    slots = _ints(slots, 'slots')
-    for b in slots:
-        if not 0 <= b < batch:
-            raise ValueError(f'encx streaming: slot {b} (0..{batch - 1})')
-    return slots
-
-
 # ---------------------------------------------------------------------------- a running session
 class _Session:
     """The device side of one SEANet stack: windows, prepared weights, LSTM state, roll tables
@@ -483,27 +423,19 @@ class _Session:
                                  bsum=torch.empty(nl * 4 * H, device=dev))
         self._weights: tp.Dict[int, torch.Tensor] = {}
         self._bias: tp.Dict[int, torch.Tensor] = {}
-        self._tables: tp.Dict[int, tuple] = {}
+        self._tables: tp.Dict[tp.Optional[int], tuple] = {}
+        # the captured steps, keyed (variant, n, first, *extra): a variant's graphs never replace
+        # another's
         self._graphs: tp.Dict[tuple, tuple] = {}
         self.started = [False] * self.B  # per slot: it has had its first chunk
         self._fresh = True               # the arena is as reset() left it
-        # the slot table the kernels read (encx.h), refilled before each step of a slots call
-        self._slots = torch.zeros(self.B, 2, device=dev, dtype=torch.int32)
-        self._slots_host: tp.Optional[tuple] = None
-        self._staging = [(torch.zeros(self.B, 2, dtype=torch.int32).pin_memory(), torch.cuda.Event())
-                         for _ in range(4)]
-        self._staged = 0
-        self._slot_graphs: tp.Dict[tuple, tuple] = {}
-        # the codebook count per slot (encx.h: nq[B]) of a per-slot-bandwidth step, beside the slot
-        # table and uploaded the same way; its graphs never replace one of the paths above
-        self._nq = torch.zeros(self.B, device=dev, dtype=torch.int32)
-        self._nq_host: tp.Optional[tuple] = None
-        self._nq_staging = [(torch.zeros(self.B, dtype=torch.int32).pin_memory(), torch.cuda.Event())
-                            for _ in range(4)]
-        self._nq_staged = 0
-        self._nq_graphs: tp.Dict[tuple, tuple] = {}
+        # the slot table the kernels read (encx.h), refilled before each step of a slots call, and
+        # beside it the codebook count per slot (encx.h: nq[B]) of a per-slot-bandwidth step
+        self.slot_table = DeviceTable(self.B, 2, dev)
+        self.nq_table = DeviceTable(self.B, 1, dev)
+        self._slots, self._nq = self.slot_table.t, self.nq_table.t
         self._cols = torch.arange(max(self._W), device=dev, dtype=torch.int32)
-        self._slot_tab = self._slot_table()
+        self._table(None)
         self.refresh_weights()
 
     # ---- weights
@@ -549,8 +481,10 @@ class _Session:
         """The named slots' next non-empty chunk is a first chunk. Host bookkeeping only: the
         `first` flag of the slot table makes the kernels refill the slot's histories and start its
         LSTM from zero on that chunk."""
-        for b in check_restart(slots, self.B):
+        slots = check_restart(slots, self.B)
+        for b in slots:
             self.started[b] = False
+        return slots
 
     def check_frames(self, frames):
         return check_frames(self.started, frames, self.min_first_frames, self.max_frames)
@@ -562,32 +496,9 @@ class _Session:
         return all(self.started) or self._fresh
 
     def put_slots(self, frames):
-        """Fill the device slot table for this step. The host runs ahead of the device, so the
-        pinned staging buffers rotate, each guarded by the event of the copy that last read it."""
-        tab = tuple((int(f), int(f > 0 and not on)) for f, on in zip(frames, self.started))
-        if tab == self._slots_host:
-            return
-        buf, ev = self._staging[self._staged]
-        self._staged = (self._staged + 1) % len(self._staging)
-        ev.synchronize()
-        buf.copy_(torch.tensor(tab, dtype=torch.int32))
-        self._slots.copy_(buf, non_blocking=True)
-        ev.record()
-        self._slots_host = tab
-
-    def put_nq(self, n_q):
-        """Fill the device nq table (a check_n_q result) for this step, as put_slots: only when it
-        changed, through rotating pinned staging."""
-        tab = tuple(int(q) for q in n_q)
-        if tab == self._nq_host:
-            return
-        buf, ev = self._nq_staging[self._nq_staged]
-        self._nq_staged = (self._nq_staged + 1) % len(self._nq_staging)
-        ev.synchronize()
-        buf.copy_(torch.tensor(tab, dtype=torch.int32))
-        self._nq.copy_(buf, non_blocking=True)
-        ev.record()
-        self._nq_host = tab
+        """Fill the device slot table for this step: per slot its frames and whether this is its
+        first chunk."""
+        self.slot_table.put((int(f), int(f > 0 and not on)) for f, on in zip(frames, self.started))
 
     def keep(self, cols, rate):
         """[B, 1, cols] bool, from the slot table on the device (capturable): the columns of a
@@ -596,9 +507,11 @@ class _Session:
 
     # ---- roll tables
     def _table(self, n):
-        """Device tables of encx_stream_win for chunks of n frames: all windows that carry a
-        history (the end-of-step roll) and the same entries one by one (the first chunk's
-        reflect fills). Built on the host, so outside any capture."""
+        """Device tables of encx_stream_win (48-byte entries) for chunks of n frames: all windows
+        that carry a history (the end-of-step roll) and the same entries one by one (the first
+        chunk's reflect fills). n None: the same for a slots step, as encx_stream_slot_win
+        (64-byte entries): the columns a row moves come from the slot table, so one table serves
+        every step. Built on the host, so outside any capture."""
         t = self._tables.get(n)
         if t is None:
             rows, full, single, index = 0, [], [], {}
@@ -606,29 +519,14 @@ class _Session:
                 if not w.P:
                     continue
                 index[wi] = len(full)
-                e = [buf.data_ptr(), self.B * w.C, w.P, n * w.rate, W]
-                full.append(e + [rows])
-                single.append(e + [0])
+                e = [buf.data_ptr(), self.B * w.C, w.P, 0 if n is None else n * w.rate, W]
+                per_slot = [w.C, w.rate] if n is None else []
+                full.append(e + [rows] + per_slot)
+                single.append(e + [0] + per_slot)
                 rows += self.B * w.C
-            tab = torch.tensor(np.array(full + single, dtype=np.int64)).to(self.dev)
+            tab = torch.tensor(np.array(full + single, dtype=np.int64)).to(self.dev) if full else None
             t = self._tables[n] = (tab, len(full), rows, index)
         return t
-
-    def _slot_table(self):
-        """The same for a slots step, as encx_stream_slot_win: the columns a row moves come from
-        the slot table, so one table serves every step."""
-        rows, full, single, index = 0, [], [], {}
-        for wi, (w, W, buf) in enumerate(zip(self.plan.windows, self._W, self.bufs)):
-            if not w.P:
-                continue
-            index[wi] = len(full)
-            e = [buf.data_ptr(), self.B * w.C, w.P, 0, W]
-            full.append(e + [rows, w.C, w.rate])
-            single.append(e + [0, w.C, w.rate])
-            rows += self.B * w.C
-        if not full:
-            return None, 0, 0, index
-        return torch.tensor(np.array(full + single, dtype=np.int64)).to(self.dev), len(full), rows, index
 
     def _reflect(self, n, wi, st, slots=False):
         """The first-chunk fill of window wi, right after its producer ran. Without the slot table
@@ -638,7 +536,7 @@ class _Session:
         if not w.P:
             return
         if slots:
-            tab, nfull, _, index = self._slot_tab
+            tab, nfull, _, index = self._table(None)
             call('encx_stream_roll_slots', tab.data_ptr() + 64 * (nfull + index[wi]), 1, self.B * w.C,
                  ROLL_REFLECT if w.fill == 'reflect' else ROLL_ZERO, self._slots.data_ptr(), self.B, st)
         elif w.fill == 'reflect':
@@ -680,80 +578,70 @@ class _Session:
                     call('encx_stream_lstm', *args, st)
             if first and L.final:
                 self._reflect(n, L.dst, st, slots)
-        if slots:
-            tab, nfull, rows, _ = self._slot_tab
-            if nfull:
-                call('encx_stream_roll_slots', tab.data_ptr(), nfull, rows, ROLL_SHIFT, self._slots.data_ptr(), B, st)
+        tab, nfull, rows, _ = self._table(None if slots else n)
+        if not nfull:
             return
-        tab, nfull, rows, _ = self._table(n)
-        if nfull:
+        if slots:
+            call('encx_stream_roll_slots', tab.data_ptr(), nfull, rows, ROLL_SHIFT, self._slots.data_ptr(), B, st)
+        else:
             call('encx_stream_roll', tab.data_ptr(), nfull, rows, 0, st)
 
-    def _run(self, graphs, key, body):
+    def _run(self, key, body):
         """body(*key) eagerly, or as the graph captured for key the first time."""
         if not self.graphs:
             return body(*key)
-        ent = graphs.get(key)
+        ent = self._graphs.get(key)
         if ent is None:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):  # one stream: the graph has no parallel branches
                 res = body(*key)
-            ent = graphs[key] = (g, res)
+            ent = self._graphs[key] = (g, res)
         ent[0].replay()
         return tuple(t.clone() for t in ent[1])  # the graph's outputs are rewritten by its next replay
 
-    def _step(self, n, body):
-        """A uniform step (see uniform()): body(n, first), keyed (n, first)."""
-        first = not all(self.started)
-        self._table(n)
-        out = self._run(self._graphs, (n, first), body)
-        self.started = [True] * self.B
+    def step(self, body, variant, frames, n, first, *extra):
+        """One step of `frames` (checked: n, first = check_frames(frames)): body(variant, n, first,
+        *extra), and a graph per such key. variant 'uniform' runs without the slot table (see
+        uniform()); 'slots', 'nq' and 'conceal' run under it (already filled: put_slots), and it is
+        read by the kernels, so one graph serves whichever slots join, sit out or deliver fewer
+        frames."""
+        if variant == 'uniform':
+            self._table(n)  # built on the host, so before any capture
+        out = self._run((variant, n, first) + extra, body)
+        if first:
+            self.started = [on or f > 0 for on, f in zip(self.started, frames)]
         self._fresh = False
         return out
 
-    def _step_slots(self, frames, n_max, any_first, body, graphs=None, extra=()):
-        """A step under the slot table (already filled: put_slots): body(n_max, any_first), keyed
-        (n_max, any_first). The table is read by the kernels, so one graph serves whichever slots
-        join, sit out or deliver fewer frames. graphs / extra: another set of graphs and further
-        key parts (the per-slot-bandwidth steps)."""
-        out = self._run(self._slot_graphs if graphs is None else graphs, (n_max, any_first) + tuple(extra), body)
-        for b, f in enumerate(frames):
-            if f:
-                self.started[b] = True
-        self._fresh = False
-        return out
+    def graph_keys(self, variant):
+        """The keys (n, first, *extra) of the variant's captured steps, sorted."""
+        return sorted(k[1:] for k in self._graphs if k[0] == variant)
 
-    def _warm(self, body, body_slots):
-        """Load every kernel of a step before any capture: one first chunk and one later chunk on
-        the zero state, eagerly, without and with the slot table; then back to a clean session."""
+    def graph(self, variant, key):
+        """The captured step (graph, outputs) of a key of graph_keys(variant)."""
+        return self._graphs[(variant,) + tuple(key)]
+
+    def first_and_one(self, variant, fill=None, *extra):
+        """The usual steps of warm(): one first chunk and one later chunk of a single frame."""
+        return [(variant, self.min_first_frames, fill) + extra, (variant, 1, fill) + extra]
+
+    def warm(self, body, runs):
+        """Load every kernel of a step before any capture. Each of `runs` starts on the zero state
+        and is a list of steps (variant, n, fill, *extra), taken eagerly with n frames for every
+        slot; fill() puts the step's tables beyond the slot table. Then back to a clean session."""
         graphs, self.graphs = self.graphs, False
         try:
-            self._step(self.min_first_frames, body)
-            self._step(1, body)
-            self.reset()
-            for n in (self.min_first_frames, 1):
-                frames = [n] * self.B
-                self.put_slots(frames)
-                self._step_slots(frames, *self.check_frames(frames), body_slots)
+            for steps in runs:
+                for variant, n, fill, *extra in steps:
+                    frames = [n] * self.B
+                    if variant != 'uniform':
+                        self.put_slots(frames)
+                    if fill is not None:
+                        fill()
+                    self.step(body, variant, frames, *self.check_frames(frames), *extra)
+                self.reset()
         finally:
             self.graphs = graphs
-        self.reset()
-
-
-def _warm_nq(s: _Session, n_q: int, body, extra=()):
-    """Load the kernels of a per-slot-bandwidth step before any capture, as _warm does: one first
-    chunk and one later chunk of a single frame (the quantizer's one-column tiling) on the zero
-    state, eagerly; then back to a clean session."""
-    graphs, s.graphs = s.graphs, False
-    try:
-        s.put_nq([n_q] * s.B)
-        for n in (s.min_first_frames, 1):
-            frames = [n] * s.B
-            s.put_slots(frames)
-            s._step_slots(frames, *s.check_frames(frames), body, s._nq_graphs, extra)
-    finally:
-        s.graphs = graphs
-    s.reset()
 
 
 def check_rvq_shape(n_q: int, bins: int, D: int):
@@ -780,26 +668,19 @@ def _embeds(model, n_q):
     return [l._codebook.embed for l in layers[:n_q]]
 
 
-class StreamEncoder:
-    """Chunked encoder of a causal model for `batch` streams: encode(x [B, C, n*hop]) -> codes
-    [B, n_q, n] (int64). n_q, the session's codebook count (the largest a slot may use with a
-    per-slot n_q), is the constructor's argument or, by default, follows from model.bandwidth. See
-    the module docstring."""
+class _Stream:
+    """What StreamEncoder and StreamDecoder share: the session of their SEANet stack (self._s),
+    the codebooks of their n_q (set before _open), and the life cycle of the slots."""
 
-    def __init__(self, model, batch: int, max_frames: int = 8, graphs: bool = True, n_q: tp.Optional[int] = None):
-        plan = encoder_plan(model)
-        if n_q is None:
-            n_q = model.quantizer.get_num_quantizers_for_bandwidth(model.frame_rate, model.bandwidth)
-        self.n_q = operator.index(n_q)  # the session's largest codebook count
-        _embeds(model, self.n_q)        # refused here, before any device call
+    def _open(self, model, plan, batch, max_frames, graphs, encode):
         self._s = _Session(model, plan, batch, max_frames, graphs)
         self.channels = model.channels
         self._embeds = _embeds(model, self.n_q)
-        self._books = _books(self._embeds, True)
-        with torch.no_grad():
-            self._s._warm(self._body, self._body_slots)
-            if self._books is not None:
-                _warm_nq(self._s, self.n_q, self._body_nq, (False,))
+        self._books = _books(self._embeds, encode)  # a decoder gathers rows: no transpose, no |e|^2
+
+    def _fill_nq(self):
+        """warm(): every slot at the session's full codebook count."""
+        self._s.nq_table.put([self.n_q] * self._s.B)
 
     hop_length = property(lambda self: self._s.hop_length)
     min_first_frames = property(lambda self: self._s.min_first_frames)
@@ -819,6 +700,27 @@ class StreamEncoder:
         if self._books is not None:
             self._books.prepare(self._embeds)
 
+
+class StreamEncoder(_Stream):
+    """Chunked encoder of a causal model for `batch` streams: encode(x [B, C, n*hop]) -> codes
+    [B, n_q, n] (int64). n_q, the session's codebook count (the largest a slot may use with a
+    per-slot n_q), is the constructor's argument or, by default, follows from model.bandwidth. See
+    the module docstring."""
+
+    def __init__(self, model, batch: int, max_frames: int = 8, graphs: bool = True, n_q: tp.Optional[int] = None):
+        plan = encoder_plan(model)
+        if n_q is None:
+            n_q = model.quantizer.get_num_quantizers_for_bandwidth(model.frame_rate, model.bandwidth)
+        self.n_q = operator.index(n_q)  # the session's largest codebook count
+        _embeds(model, self.n_q)        # refused here, before any device call
+        self._open(model, plan, batch, max_frames, graphs, True)
+        s = self._s
+        runs = [s.first_and_one('uniform'), s.first_and_one('slots')]
+        if self._books is not None:
+            runs.append(s.first_and_one('nq', self._fill_nq, False))
+        with torch.no_grad():
+            s.warm(self._body, runs)
+
     def n_q_for(self, bandwidth_kbps: float) -> int:
         """The codebook count of this model at a bandwidth (kbps), for encode_slots(n_q=...).
         ValueError when the session was built for fewer codebooks."""
@@ -828,34 +730,28 @@ class StreamEncoder:
             raise ValueError(f'encx streaming: {bandwidth_kbps} kbps needs {q} codebooks, the session has {self.n_q}')
         return q
 
-    def _body_nq(self, n, first, latent):
-        """A slots step whose quantizer is the fused kernel under the nq table: the latent is read
-        in place from the last window, all slots and layers in one launch."""
+    def _body(self, variant, n, first, latent=True):
+        """One step -> (codes, latent). 'uniform': the layers without the slot table, the
+        per-layer quantizer. 'slots': under the table, the columns past a slot's count zero.
+        'nq': under the table, the quantizer the fused kernel under the nq table, which reads the
+        latent in place from the last window, all slots and layers in one launch; the latent is
+        returned only when asked for."""
         s = self._s
-        s._layers(n, first, slots=True)
+        s._layers(n, first, variant != 'uniform')
         dst = s.plan.layers[-1].dst
-        win = s.bufs[dst][:, :, s.plan.windows[dst].P:][:, :, :n]
-        codes = ops.stream_rvq_encode_slots(win, self._books, s._slots, s._nq)
-        if not latent:
-            return (codes,)
-        return codes, torch.where(s.keep(n, 1), win, 0.).contiguous()
-
-    def _body(self, n, first):
-        s = self._s
-        s._layers(n, first)
-        # a copy, never a view: the window is rewritten by the next step
-        emb = s.bufs[s.plan.layers[-1].dst][:, :, :n].clone(memory_format=torch.contiguous_format)
-        codes = ops.rvq_encode(emb, self._embeds).permute(1, 0, 2).contiguous()
-        return codes, emb
-
-    def _body_slots(self, n, first):
-        s = self._s
-        s._layers(n, first, slots=True)
+        P = s.plan.windows[dst].P
+        win = s.bufs[dst][:, :, P:P + n]
+        if variant == 'uniform':
+            # a copy, never a view: the window is rewritten by the next step
+            emb = win.clone(memory_format=torch.contiguous_format)
+            return ops.rvq_encode(emb, self._embeds).permute(1, 0, 2).contiguous(), emb
+        if variant == 'nq':
+            codes = ops.stream_rvq_encode_slots(win, self._books, s._slots, s._nq)
+            return (codes, torch.where(s.keep(n, 1), win, 0.).contiguous()) if latent else (codes,)
         keep = s.keep(n, 1)
         # the columns past a slot's count are zero (and a copy, as above)
-        emb = torch.where(keep, s.bufs[s.plan.layers[-1].dst][:, :, :n], 0.).contiguous()
-        codes = torch.where(keep, ops.rvq_encode(emb, self._embeds).permute(1, 0, 2), 0).contiguous()
-        return codes, emb
+        emb = torch.where(keep, win, 0.).contiguous()
+        return torch.where(keep, ops.rvq_encode(emb, self._embeds).permute(1, 0, 2), 0).contiguous(), emb
 
     def _samples(self, x):
         s = self._s
@@ -871,13 +767,14 @@ class StreamEncoder:
         uniform case of encode_slots: every slot delivers n frames."""
         s = self._s
         n = self._samples(x)
-        s.check_frames([n] * s.B)
+        frames = [n] * s.B
+        n, first = s.check_frames(frames)
         ops._check(x)
         if not s.uniform():  # some slots are on their first chunk, others not
-            return self.encode_slots(x, [n] * s.B, return_latent)
+            return self.encode_slots(x, frames, return_latent)
         P = s.plan.windows[0].P
         s.bufs[0][:, :, P:P + x.shape[2]].copy_(x)
-        codes, emb = s._step(n, self._body)
+        codes, emb = s.step(self._body, 'uniform', frames, n, first)
         return (codes, emb) if return_latent else codes
 
     @torch.no_grad()
@@ -907,14 +804,14 @@ class StreamEncoder:
         P = s.plan.windows[0].P
         s.bufs[0][:, :, P:P + x.shape[2]].copy_(torch.where(s.keep(x.shape[2], s.hop_length), x, 0.))
         if n_q is not None:
-            s.put_nq(n_q)
-            out = s._step_slots(frames, n_max, any_first, self._body_nq, s._nq_graphs, (bool(return_latent),))
-            return out if return_latent else out[0]
-        codes, emb = s._step_slots(frames, n_max, any_first, self._body_slots)
-        return (codes, emb) if return_latent else codes
+            s.nq_table.put(n_q)
+            out = s.step(self._body, 'nq', frames, n_max, any_first, bool(return_latent))
+        else:
+            out = s.step(self._body, 'slots', frames, n_max, any_first)
+        return out if return_latent else out[0]
 
 
-class StreamDecoder:
+class StreamDecoder(_Stream):
     """Chunked decoder of a causal model for `batch` streams: decode(codes [B, n_q, n]) -> wav
     [B, C, n * hop_length]. See the module docstring."""
 
@@ -927,35 +824,28 @@ class StreamDecoder:
         # the fade of a concealed slot (module docstring): frames held, frames down, frames back up
         self._M = fade_span(conceal_hold, conceal_fade, conceal_recover, plan.hop_length)
         self._hold, self._fade, self._recover = int(conceal_hold), int(conceal_fade), int(conceal_recover)
-        self._s = _Session(model, plan, batch, max_frames, graphs)
-        self.channels = model.channels
+        self._open(model, plan, batch, max_frames, graphs, False)
         self.bins = model.quantizer.bins
-        self._embeds = _embeds(model, self.n_q)
-        self._codes: tp.Dict[int, torch.Tensor] = {}
-        self._codes_nq: tp.Dict[int, torch.Tensor] = {}
-        self._books = _books(self._embeds, False)  # a decoder gathers rows: no transpose, no |e|^2
+        self._codes: tp.Dict[tuple, torch.Tensor] = {}
         # concealment: per slot the fade position p (0..M) and the samples r of the current loss run,
-        # advanced here exactly as the kernels do, and the table they read (encx.h: conceal[B][4]),
-        # uploaded as the slot table is; its graphs never replace one of the other paths
-        B, dev = self._s.B, self._s.dev
-        self._p, self._r = [self._M] * B, [0] * B
+        # advanced here exactly as the kernels do, and the table they read (encx.h: conceal[B][4])
+        s = self._s
+        self._p, self._r = [self._M] * s.B, [0] * s.B
         self._dirty = False  # some slot has p < M or r > 0
-        self._ct = torch.zeros(B, 4, device=dev, dtype=torch.int32)
-        self._ct_host: tp.Optional[tuple] = None
-        self._ct_staging = [(torch.zeros(B, 4, dtype=torch.int32).pin_memory(), torch.cuda.Event())
-                            for _ in range(4)]
-        self._ct_staged = 0
-        self._conceal_graphs: tp.Dict[tuple, tuple] = {}
-        with torch.no_grad():
-            self._s._warm(self._body, self._body_slots)
+        self._conceal = DeviceTable(s.B, 4, s.dev)
+        runs = [s.first_and_one('uniform'), s.first_and_one('slots')]
+        if self._books is not None:
+            runs.append(s.first_and_one('nq', self._fill_nq))
+        if plan.windows[0].P:
+            # the concealed step: a first chunk, then one concealed frame for every slot on either
+            # dequantizer
+            steps = [('slots', s.min_first_frames, None),
+                     ('conceal', 1, lambda: self._put_conceal([True] * s.B), False)]
             if self._books is not None:
-                _warm_nq(self._s, self.n_q, self._body_nq)
-            if plan.windows[0].P:
-                self._warm_conceal()
-
-    hop_length = property(lambda self: self._s.hop_length)
-    min_first_frames = property(lambda self: self._s.min_first_frames)
-    plan = property(lambda self: self._s.plan)
+                steps.append(('conceal', 1, self._fill_nq, True))
+            runs.append(steps)
+        with torch.no_grad():
+            s.warm(self._body, runs)
 
     def reset(self):
         self._s.reset()
@@ -963,31 +853,14 @@ class StreamDecoder:
 
     def restart(self, slots):
         """As StreamEncoder.restart; the slots' fade starts over at full level."""
-        self._s.restart(slots)
-        for b in check_restart(slots, self._s.B):
+        for b in self._s.restart(slots):
             self._p[b], self._r[b] = self._M, 0
         self._dirty = any(p < self._M or r for p, r in zip(self._p, self._r))
 
-    def refresh_weights(self):
-        self._s.refresh_weights()
-        self._embeds = _embeds(self._s.model, self.n_q)
-        if self._books is not None:
-            self._books.prepare(self._embeds)
-
     # ---- concealment
     def _put_conceal(self, lost):
-        """Fill the device concealment table for this step (lost flag, p and r at its start), as
-        _Session.put_slots: only when it changed, through rotating pinned staging."""
-        tab = tuple((int(l), p, r, 0) for l, p, r in zip(lost, self._p, self._r))
-        if tab == self._ct_host:
-            return
-        buf, ev = self._ct_staging[self._ct_staged]
-        self._ct_staged = (self._ct_staged + 1) % len(self._ct_staging)
-        ev.synchronize()
-        buf.copy_(torch.tensor(tab, dtype=torch.int32))
-        self._ct.copy_(buf, non_blocking=True)
-        ev.record()
-        self._ct_host = tab
+        """Fill the device concealment table for this step: lost flag, p and r at its start."""
+        self._conceal.put((int(l), p, r, 0) for l, p, r in zip(lost, self._p, self._r))
 
     def _advance(self, frames, lost):
         """p and r of every slot after the step, by the rule the output kernel applies per sample."""
@@ -999,86 +872,46 @@ class StreamDecoder:
                                                self._hold * hop, self._fade, self._recover, self._M)
         self._dirty = any(p < self._M or r for p, r in zip(self._p, self._r))
 
-    def _body_conceal(self, n, first, fused):
-        """A slots step with lost or fading slots. The latent of a lost slot is its held column
-        (P-1 of the first window), set by the fused dequantizer itself or, after the per-layer
-        one, by the fill kernel; the output kernel reads the last window in place, zeroes the
-        samples past each slot's count and applies the fade."""
+    def _code_buf(self, n, fused=False):
+        """The codes of a step, the graph's own input: [n_q, B, n] for the per-layer dequantizer,
+        clamped and zero past a slot's count; fused, [B, n_q, n] as the caller passed them (the
+        kernel clamps them and reads neither a slot's tail nor its rows k >= n_q[b])."""
+        c = self._codes.get((n, fused))
+        if c is None:
+            shape = (self._s.B, self.n_q, n) if fused else (self.n_q, self._s.B, n)
+            c = self._codes[n, fused] = torch.zeros(shape, device=self._s.dev, dtype=torch.int64)
+        return c
+
+    def _body(self, variant, n, first, fused=False):
+        """One step -> (wav,). The dequantizer writes into the first window behind its history:
+        per layer, or ('nq', and 'conceal' with fused) the fused kernel under the nq table. Then the
+        layers, without the slot table ('uniform') or under it, and the output, a copy of the last
+        window, zero past a slot's count under the table. 'conceal': a slots step with lost or
+        fading slots. The latent of a lost slot is its held column (P-1 of the first window), set
+        by the fused dequantizer itself or, after the per-layer one, by the fill kernel; the output
+        kernel reads the last window in place, zeroes the samples past each slot's count and
+        applies the fade."""
         s = self._s
-        P, win = s.plan.windows[0].P, s.bufs[0]
-        if fused:
-            ops.stream_rvq_decode_slots(self._code_buf_nq(n), self._books, s._slots, s._nq, win[:, :, P:P + n],
-                                        self._ct, win[:, :, P - 1:P])
+        P, win, hop = s.plan.windows[0].P, s.bufs[0], s.hop_length
+        conceal = variant == 'conceal'
+        if fused or variant == 'nq':
+            held = (self._conceal.t, win[:, :, P - 1:P]) if conceal else ()
+            ops.stream_rvq_decode_slots(self._code_buf(n, True), self._books, s._slots, s._nq, win[:, :, P:P + n],
+                                        *held)
         else:
             win[:, :, P:P + n].copy_(ops.rvq_decode(self._code_buf(n), self._embeds))
-            ops.stream_conceal_fill(win, P, n, s._slots, self._ct)
-        s._layers(n, first, slots=True)
-        return (ops.stream_conceal_out(s.bufs[s.plan.layers[-1].dst], s.hop_length, n, s._slots, self._ct,
-                                       self._hold, self._fade, self._recover),)
-
-    def _warm_conceal(self):
-        """Load the kernels of a concealed step before any capture, as _warm_nq does: a first chunk,
-        then one concealed frame for every slot on either dequantizer, eagerly; then a clean session."""
-        s = self._s
-        graphs, s.graphs = s.graphs, False
-        try:
-            frames = [s.min_first_frames] * s.B
-            s.put_slots(frames)
-            s._step_slots(frames, *s.check_frames(frames), self._body_slots)
-            frames = [1] * s.B
-            s.put_slots(frames)
-            self._put_conceal([True] * s.B)
-            self._body_conceal(1, False, False)
-            if self._books is not None:
-                s.put_nq([self.n_q] * s.B)
-                self._body_conceal(1, False, True)
-        finally:
-            s.graphs = graphs
-        s.reset()
-
-    def _code_buf_nq(self, n):
-        """The codes of a per-slot-bandwidth step as the caller passed them, [B, n_q, n]: the
-        kernel clamps them and reads neither a slot's tail nor its rows k >= n_q[b]."""
-        c = self._codes_nq.get(n)
-        if c is None:
-            c = self._codes_nq[n] = torch.zeros(self._s.B, self.n_q, n, device=self._s.dev, dtype=torch.int64)
-        return c
-
-    def _body_nq(self, n, first):
-        """A slots step whose dequantizer is the fused kernel under the nq table, written straight
-        into the first window behind its history."""
-        s = self._s
-        P = s.plan.windows[0].P
-        ops.stream_rvq_decode_slots(self._code_buf_nq(n), self._books, s._slots, s._nq, s.bufs[0][:, :, P:P + n])
-        s._layers(n, first, slots=True)
-        out = s.bufs[s.plan.layers[-1].dst][:, :, :n * s.hop_length]
-        return (torch.where(s.keep(n * s.hop_length, s.hop_length), out, 0.).contiguous(),)
-
-    def _code_buf(self, n):
-        c = self._codes.get(n)
-        if c is None:
-            c = self._codes[n] = torch.zeros(self.n_q, self._s.B, n, device=self._s.dev, dtype=torch.int64)
-        return c
-
-    def _body(self, n, first):
-        s = self._s
-        q = ops.rvq_decode(self._code_buf(n), self._embeds)
-        P = s.plan.windows[0].P
-        s.bufs[0][:, :, P:P + n].copy_(q)
-        s._layers(n, first)
-        # a copy, never a view: the window is rewritten by the next step
-        out = s.bufs[s.plan.layers[-1].dst][:, :, :n * s.hop_length]
-        return (out.clone(memory_format=torch.contiguous_format),)
-
-    def _body_slots(self, n, first):
-        s = self._s
-        q = ops.rvq_decode(self._code_buf(n), self._embeds)
-        P = s.plan.windows[0].P
-        s.bufs[0][:, :, P:P + n].copy_(q)
-        s._layers(n, first, slots=True)
-        # the samples past a slot's count are zero (and a copy, as above)
-        out = s.bufs[s.plan.layers[-1].dst][:, :, :n * s.hop_length]
-        return (torch.where(s.keep(n * s.hop_length, s.hop_length), out, 0.).contiguous(),)
+            if conceal:
+                ops.stream_conceal_fill(win, P, n, s._slots, self._conceal.t)
+        s._layers(n, first, variant != 'uniform')
+        out = s.bufs[s.plan.layers[-1].dst]
+        if conceal:
+            return (ops.stream_conceal_out(out, hop, n, s._slots, self._conceal.t, self._hold, self._fade,
+                                           self._recover),)
+        out = out[:, :, :n * hop]
+        if variant == 'uniform':
+            # a copy, never a view: the window is rewritten by the next step
+            return (out.clone(memory_format=torch.contiguous_format),)
+        return (torch.where(s.keep(n * hop, hop), out, 0.).contiguous(),)
 
     def _frames(self, codes):
         s = self._s
@@ -1093,16 +926,16 @@ class StreamDecoder:
         the offline decoder on the codes so far. Codes are clamped to the codebook size. The
         uniform case of decode_slots: every slot delivers n frames."""
         s = self._s
-        n = self._frames(codes)
-        s.check_frames([n] * s.B)
+        frames = [self._frames(codes)] * s.B
+        n, first = s.check_frames(frames)
         if not codes.is_cuda:
             raise RuntimeError('encx streaming takes device tensors (no CPU fallback)')
         if not s.uniform() or self._dirty:  # some slots are on their first chunk, or in a fade
-            return self.decode_slots(codes, [n] * s.B)
+            return self.decode_slots(codes, frames)
         buf = self._code_buf(n)
         buf.copy_(codes.permute(1, 0, 2))
         buf.clamp_(0, self.bins - 1)  # an index outside the codebook must never reach the gather
-        return s._step(n, self._body)[0]
+        return s.step(self._body, 'uniform', frames, n, first)[0]
 
     @torch.no_grad()
     def decode_slots(self, codes: tp.Optional[torch.Tensor], frames: tp.Sequence[int],
@@ -1144,26 +977,19 @@ class StreamDecoder:
         conceal = lost is not None or any(p < self._M for p in self._p)
         if conceal:
             self._put_conceal(lost or [False] * s.B)
-        if n_q is not None:
-            s.put_nq(n_q)
-            buf = self._code_buf_nq(n_max)
-            buf.zero_() if codes is None else buf.copy_(codes)
-            if conceal:
-                out = s._step_slots(frames, n_max, any_first, self._body_conceal, self._conceal_graphs, (True,))[0]
-            else:
-                out = s._step_slots(frames, n_max, any_first, self._body_nq, s._nq_graphs)[0]
-            self._advance(frames, lost)
-            return out
-        buf = self._code_buf(n_max)
+        fused = n_q is not None
+        if fused:
+            s.nq_table.put(n_q)
+        buf = self._code_buf(n_max, fused)
         if codes is None:
             buf.zero_()
+        elif fused:
+            buf.copy_(codes)
         else:
             # clamped as in decode(); past a slot's count whatever the caller left becomes code 0
             buf.copy_(torch.where(s.keep(n_max, 1).squeeze(1), codes.permute(1, 0, 2).clamp(0, self.bins - 1), 0))
-        if conceal:
-            out = s._step_slots(frames, n_max, any_first, self._body_conceal, self._conceal_graphs, (False,))[0]
-        else:
-            out = s._step_slots(frames, n_max, any_first, self._body_slots)[0]
+        variant, extra = ('conceal', (fused,)) if conceal else ('nq' if fused else 'slots', ())
+        out = s.step(self._body, variant, frames, n_max, any_first, *extra)[0]
         self._advance(frames, lost)
         return out
 
@@ -1205,6 +1031,9 @@ class _Packets:
         if lm_format == 2 and not use_lm:
             raise ValueError('encx streaming: lm_format=2 is an LM-coded packet: it goes with use_lm=True')
         self.slot_n_q, self.lm_format = bool(slot_n_q), int(lm_format)
+        # the header: the byte n, or the bytes (n, K) of the packets with a codebook count per slot
+        self._hdr = 2 if self.slot_n_q or self.lm_format == 2 else 1
+        self._packet_bytes = packet_bytes_nq if self._hdr == 2 else packet_bytes
         if not 1 <= batch <= MAX_BATCH:
             raise ValueError(f'encx streaming: batch {batch} (1..{MAX_BATCH})')
         if not 1 <= n_q <= min(model.quantizer.n_q, 64):
@@ -1240,30 +1069,22 @@ class _Packets:
             if dev.type != 'cuda':
                 raise RuntimeError('encx streaming runs on the GPU (no CPU fallback): move the model first')
             ensure_device(dev)
-            self._stride = (packet_bytes_nq if self.slot_n_q else packet_bytes)(self.max_frames, self.n_q, self.bits)
-            self._slots = torch.zeros(self.B, 2, dtype=torch.int32, device=dev)
-            self._nq = torch.zeros(self.B, dtype=torch.int32, device=dev)
-            self._nq_tab = None
+            self._stride = self._packet_bytes(self.max_frames, self.n_q, self.bits)
+            self._slots = DeviceTable(self.B, 2, dev)
+            self._nq = DeviceTable(self.B, 1, dev)
             self._bytes = torch.zeros(self.B, self._stride, dtype=torch.uint8, device=dev)
             self._nbytes = torch.zeros(self.B, dtype=torch.int64, device=dev)
             self._err = torch.zeros(1, dtype=torch.int32, device=dev)
-            self._tab = None
             self._dev = dev
 
-    def _put_slots(self, frames):
-        """The raw form's slot table (no first-chunk flag: it carries no state), uploaded only
-        when it differs from the last step's."""
-        tab = [(int(f), 0) for f in frames]
-        if tab != self._tab:
-            self._slots.copy_(torch.tensor(tab, dtype=torch.int32))
-            self._tab = tab
-
-    def _put_nq(self, n_q):
-        """The nq table of a variable-bandwidth step, uploaded only when it changed."""
-        tab = [int(q) for q in n_q]
-        if tab != self._nq_tab:
-            self._nq.copy_(torch.tensor(tab, dtype=torch.int32))
-            self._nq_tab = tab
+    def _put(self, frames, n_q):
+        """The raw form's tables for this step: the slot table (no first-chunk flag: it carries
+        no state) and, for variable-bandwidth packets, nq -> the kernel's nq argument, if any."""
+        self._slots.put([(f, 0) for f in frames])
+        if n_q is None:
+            return ()
+        self._nq.put(n_q)
+        return (self._nq.data_ptr(),)
 
 
 class StreamPacker(_Packets):
@@ -1281,7 +1102,6 @@ class StreamPacker(_Packets):
 
     def __init__(self, model, batch: int, n_q: int, use_lm: bool = False, lm=None, max_frames: int = 8,
                  graphs: bool = True, slot_n_q: bool = False, lm_format: int = 1):
-        from .lm import LMStreamEncoder
         super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamEncoder, slot_n_q, lm_format)
 
     @torch.no_grad()
@@ -1304,27 +1124,18 @@ class StreamPacker(_Packets):
         if not codes.is_cuda:
             raise RuntimeError('encx streaming takes device tensors (no CPU fallback)')
         self._ensure()
-        self._put_slots(frames)
+        nq = self._put(frames, n_q)
         self._err.zero_()
         sb, sk, s_t = codes.stride()
-        if n_q is not None:
-            self._put_nq(n_q)
-            call('encx_bitpack_slots_nq', codes.data_ptr(), sb, sk, s_t, self.B, self.n_q, n_max, self.bits,
-                 self._slots.data_ptr(), self._nq.data_ptr(), self._bytes.data_ptr(), self._stride,
-                 self._nbytes.data_ptr(), self._err.data_ptr(), stream())
-            host = self._bytes.cpu()
-            if int(self._err.item()):
-                raise ValueError(f'encx streaming: a delivered code does not fit in {self.bits} bits')
-            return [host[b, :packet_bytes_nq(f, q, self.bits)].numpy().tobytes() if f else b''
-                    for b, (f, q) in enumerate(zip(frames, n_q))]
-        call('encx_bitpack_slots', codes.data_ptr(), sb, sk, s_t, self.B, self.n_q, n_max, self.bits,
-             self._slots.data_ptr(), self._bytes.data_ptr(), self._stride, self._nbytes.data_ptr(),
-             self._err.data_ptr(), stream())
+        call('encx_bitpack_slots_nq' if nq else 'encx_bitpack_slots', codes.data_ptr(), sb, sk, s_t, self.B,
+             self.n_q, n_max, self.bits, self._slots.data_ptr(), *nq, self._bytes.data_ptr(), self._stride,
+             self._nbytes.data_ptr(), self._err.data_ptr(), stream())
         host = self._bytes.cpu()
         if int(self._err.item()):
             raise ValueError(f'encx streaming: a delivered code does not fit in {self.bits} bits')
-        return [host[b, :packet_bytes(f, self.n_q, self.bits)].numpy().tobytes() if f else b''
-                for b, f in enumerate(frames)]
+        size, bits = self._packet_bytes, self.bits
+        return [host[b, :size(f, q, bits)].numpy().tobytes() if f else b''
+                for b, (f, q) in enumerate(zip(frames, n_q or [self.n_q] * self.B))]
 
 
 class StreamUnpacker(_Packets):
@@ -1338,7 +1149,6 @@ class StreamUnpacker(_Packets):
 
     def __init__(self, model, batch: int, n_q: int, use_lm: bool = False, lm=None, max_frames: int = 8,
                  graphs: bool = True, slot_n_q: bool = False, lm_format: int = 1):
-        from .lm import LMStreamDecoder
         super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamDecoder, slot_n_q, lm_format)
 
     @property
@@ -1371,54 +1181,39 @@ class StreamUnpacker(_Packets):
         return kept
 
     def _headers(self, packets):
-        if len(packets) != self.B:
-            raise ValueError(f'encx streaming: packets for {len(packets)} slots, the session has {self.B}')
-        frames = []
-        for b, p in enumerate(packets):
-            if not isinstance(p, (bytes, bytearray)):
-                raise ValueError(f'encx streaming: the packet of slot {b} is not bytes')
-            n = p[0] if len(p) else 0
-            if len(p) and not 1 <= n <= self.max_frames:
-                raise ValueError(f'encx streaming: the packet of slot {b} announces {n} frames '
-                                 f'(1..max_frames={self.max_frames})')
-            if len(p) and not self.use_lm and len(p) != packet_bytes(n, self.n_q, self.bits):
-                raise ValueError(f'encx streaming: a raw packet of {n} frames in slot {b} has '
-                                 f'{packet_bytes(n, self.n_q, self.bits)} bytes, not {len(p)}')
-            frames.append(int(n))
-        if not any(frames):
-            raise ValueError('encx streaming: no slot delivers a frame')
-        return frames
-
-    def _headers_nq(self, packets):
-        """The (n, K) headers of variable-bandwidth packets -> (frames, n_q), 0 and 0 for b''."""
+        """The headers of a step's packets, the byte n or the bytes (n, K) -> (frames, n_q), 0 and
+        0 for b''. With the one-byte header K is the session's n_q."""
         if len(packets) != self.B:
             raise ValueError(f'encx streaming: packets for {len(packets)} slots, the session has {self.B}')
         frames, n_q = [], []
+        hdr, K_max, raw = self._hdr, self.n_q, not self.use_lm
         for b, p in enumerate(packets):
             if not isinstance(p, (bytes, bytearray)):
                 raise ValueError(f'encx streaming: the packet of slot {b} is not bytes')
-            n, K = (p[0], p[1]) if len(p) >= 2 else (0, 0)
+            n = K = 0
             if len(p):
-                if len(p) < 2:
+                if len(p) < hdr:
                     raise ValueError(f'encx streaming: the packet of slot {b} has no (n, K) header')
+                n, K = p[0], p[1] if hdr == 2 else K_max
                 if not 1 <= n <= self.max_frames:
                     raise ValueError(f'encx streaming: the packet of slot {b} announces {n} frames '
                                      f'(1..max_frames={self.max_frames})')
-                if not 1 <= K <= self.n_q:
+                if not 1 <= K <= K_max:
                     raise ValueError(f'encx streaming: the packet of slot {b} announces {K} codebooks '
-                                     f'(1..n_q={self.n_q})')
-                if self.lm_format == 2:
-                    if len(p) - 2 > self._lm.cap:
-                        raise ValueError(f'encx streaming: a payload of {len(p) - 2} bytes in slot {b}; no packet of '
-                                         f'up to {self.max_frames} frames has more than {self._lm.cap}')
-                elif len(p) != packet_bytes_nq(n, K, self.bits):
-                    raise ValueError(f'encx streaming: a packet of {n} frames of {K} codebooks in slot {b} has '
-                                     f'{packet_bytes_nq(n, K, self.bits)} bytes, not {len(p)}')
-            frames.append(int(n))
-            n_q.append(int(K))
+                                     f'(1..n_q={K_max})')
+                if raw and len(p) != self._packet_bytes(n, K, self.bits):
+                    raise ValueError(f'encx streaming: a raw packet of {n} frames of {K} codebooks in slot {b} has '
+                                     f'{self._packet_bytes(n, K, self.bits)} bytes, not {len(p)}')
+                if self.lm_format == 2 and len(p) - 2 > self._lm.cap:
+                    raise ValueError(f'encx streaming: a payload of {len(p) - 2} bytes in slot {b}; no packet of '
+                                     f'up to {self.max_frames} frames has more than {self._lm.cap}')
+            frames.append(n)
+            n_q.append(K)
         if not any(frames):
             raise ValueError('encx streaming: no slot delivers a frame')
         return frames, n_q
+
+    _headers_nq = _headers  # its name for the (n, K) form
 
     def _upload(self, packets):
         host = torch.zeros(self.B, self._stride, dtype=torch.uint8)
@@ -1436,37 +1231,19 @@ class StreamUnpacker(_Packets):
         if packets is None:  # every packet of the step belongs to a lost slot: nothing to decode
             codes = torch.zeros(self.B, self.n_q, 0, dtype=torch.int64, device=next(self.model.parameters()).device)
             return (codes, [0] * self.B, [0] * self.B) if self.lm_format == 2 else (codes, [0] * self.B)
-        if self.lm_format == 2:
-            frames, n_q = self._headers_nq(packets)
-            codes, failed = self._lm.decode_slots([bytes(p[2:]) for p in packets], frames, n_q)
-            return (codes, [0 if b in failed else f for b, f in enumerate(frames)],
-                    [0 if b in failed else q for b, q in enumerate(n_q)])
-        if self.slot_n_q:
-            frames, n_q = self._headers_nq(packets)
+        frames, n_q = self._headers(packets)
+        if self._lm is not None:
+            codes, failed = self._lm.decode_slots([bytes(p[self._hdr:]) for p in packets], frames,
+                                                  n_q if self._hdr == 2 else None)
+            frames, n_q = ([0 if b in failed else v for b, v in enumerate(vs)] for vs in (frames, n_q))
+        else:
             n_max = max(frames)
             self._ensure()
             self._upload(packets)
-            self._put_slots(frames)
-            self._put_nq(n_q)
+            nq = self._put(frames, n_q if self._hdr == 2 else None)
             codes = torch.empty(self.B, self.n_q, n_max, dtype=torch.int64, device=self._dev)
             sb, sk, s_t = codes.stride()
-            call('encx_bitunpack_slots_nq', self._bytes.data_ptr() + 2, self._stride, self.B, self.n_q, n_max,
-                 self.bits, self._slots.data_ptr(), self._nq.data_ptr(), codes.data_ptr(), sb, sk, s_t, stream())
-            return codes, frames, n_q
-        frames = self._headers(packets)
-        if self._lm is not None:
-            codes, failed = self._lm.decode_slots([bytes(p[1:]) for p in packets], frames)
-            return codes, [0 if b in failed else f for b, f in enumerate(frames)]
-        n_max = max(frames)
-        self._ensure()
-        host = torch.zeros(self.B, self._stride, dtype=torch.uint8)
-        for b, p in enumerate(packets):
-            if len(p):
-                host[b, :len(p)] = torch.frombuffer(bytearray(p), dtype=torch.uint8)
-        self._bytes.copy_(host)
-        self._put_slots(frames)
-        codes = torch.empty(self.B, self.n_q, n_max, dtype=torch.int64, device=self._dev)
-        sb, sk, s_t = codes.stride()
-        call('encx_bitunpack_slots', self._bytes.data_ptr() + 1, self._stride, self.B, self.n_q, n_max, self.bits,
-             self._slots.data_ptr(), codes.data_ptr(), sb, sk, s_t, stream())
-        return codes, frames
+            call('encx_bitunpack_slots_nq' if nq else 'encx_bitunpack_slots', self._bytes.data_ptr() + self._hdr,
+                 self._stride, self.B, self.n_q, n_max, self.bits, self._slots.data_ptr(), *nq, codes.data_ptr(),
+                 sb, sk, s_t, stream())
+        return (codes, frames, n_q) if self._hdr == 2 else (codes, frames)

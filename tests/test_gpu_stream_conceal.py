@@ -220,7 +220,7 @@ def test_one_graph_serves_every_loss_pattern(ctx, fused):
     kw = dict(conceal_hold=0, conceal_fade=1, conceal_recover=2)
     dec = decoder(ctx.m, 2, ctx.n_q, **kw)
     got = drive(dec, ctx.codes[:2], steps, n_q=nq, none_ok=True)
-    assert sorted(dec._conceal_graphs) == [(1, False, fused), (3, False, fused)]
+    assert dec._s.graph_keys('conceal') == [(1, False, fused), (3, False, fused)]
     want = drive(decoder(ctx.m, 2, ctx.n_q, graphs=False, **kw), ctx.codes[:2], steps, n_q=nq, none_ok=True)
     for b in range(2):
         assert torch.equal(got[b], want[b]), b
@@ -241,17 +241,17 @@ def test_sessions_that_never_lose_are_untouched(ctx):
         assert torch.equal(ya, yb)
         for s, f in enumerate(fr):
             assert torch.equal(ya[s:s + 1, :, :f * HOP], ctx.solo[s][2][:, :, (off[s] - f) * HOP:off[s] * HOP])
-    assert a._conceal_graphs == {} and b._conceal_graphs == {} and not b._dirty
+    assert a._s.graph_keys('conceal') == [] and b._s.graph_keys('conceal') == [] and not b._dirty
     # a loss, the way back to full level, and then the old path again
     dec = decoder(ctx.m, 1, ctx.n_q, conceal_hold=0, conceal_fade=1, conceal_recover=1)
     sched = ((OK, 7), (LOST, 1), (OK, 1), (OK, 5), (OK, 1))
     codes = [ctx.codes[0]]
     w = drive(dec, codes, [(s,) for s in sched[:3]])[0]
-    assert dec._p == [dec._M] and not dec._dirty and sorted(dec._conceal_graphs) == [(1, False, False)]
-    assert (5, False) not in dec._s._slot_graphs
+    assert dec._p == [dec._M] and not dec._dirty and dec._s.graph_keys('conceal') == [(1, False, False)]
+    assert (5, False) not in dec._s.graph_keys('slots')
     rep = repeated(ctx.codes[0], sched)
     y = dec.decode_slots(rep[:, :, 9:14], [5], lost=[False])
-    assert (5, False) in dec._s._slot_graphs and sorted(dec._conceal_graphs) == [(1, False, False)]
+    assert (5, False) in dec._s.graph_keys('slots') and dec._s.graph_keys('conceal') == [(1, False, False)]
     plain, _ = stream_decode(ctx.m, rep[:, :, :14], (7, 1, 1, 5))
     assert torch.equal(y, plain[:, :, 9 * HOP:])
     pos, M = rule(sched[:3], 0, 1, 1)
@@ -280,7 +280,7 @@ def test_refusals_leave_the_session_untouched(ctx):
         with pytest.raises(ValueError, match=what):
             dec.decode_slots(codes, frames, lost=lost)
         assert torch.equal(dec._s._arena, state) and dec._s.started == [True, False]
-        assert dec._p == twin._p and dec._r == twin._r and dec._conceal_graphs == {}
+        assert dec._p == twin._p and dec._r == twin._r and dec._s.graph_keys('conceal') == []
     for codes, frames, lost in ((None, [2, 0], [True, False]), (c[:, :, 9:16], [1, 7], [False, False])):
         assert torch.equal(dec.decode_slots(codes, frames, lost=lost), twin.decode_slots(codes, frames, lost=lost))
 

@@ -178,8 +178,8 @@ def test_session_at_constant_per_slot_n_q(ctx, run1):
         assert torch.equal(codes[:, :k], s_codes), b
         assert torch.equal(wave, s_wave), b
     # keyed apart from the graphs of the path without n_q
-    assert not enc._s._slot_graphs and not dec._s._slot_graphs
-    assert enc._s._nq_graphs and dec._s._nq_graphs
+    assert not enc._s.graph_keys('slots') and not dec._s.graph_keys('slots')
+    assert enc._s.graph_keys('nq') and dec._s.graph_keys('nq')
 
 
 def test_bandwidth_change_mid_stream(ctx):
@@ -220,9 +220,9 @@ def test_graph_replay_reads_the_nq_table_on_the_device(ctx):
     nqs = ((8, 8, 8), (1, 3, 8), (8, 2, 5), (4, 8, 1))
     eager, e_enc, _ = drive(ctx.m, ctx.clips, schedule, nqs, graphs=False)
     graph, g_enc, g_dec = drive(ctx.m, ctx.clips, schedule, nqs)
-    assert not e_enc._s._nq_graphs
-    assert sorted(g_enc._s._nq_graphs) == [(3, False, False), (7, True, False)]
-    assert sorted(g_dec._s._nq_graphs) == [(3, False), (7, True)]
+    assert not e_enc._s.graph_keys('nq')
+    assert g_enc._s.graph_keys('nq') == [(3, False, False), (7, True, False)]
+    assert g_dec._s.graph_keys('nq') == [(3, False), (7, True)]
     for b in range(3):
         assert torch.equal(graph[b][0], eager[b][0]) and torch.equal(graph[b][1], eager[b][1]), b
         assert int(graph[b][0][:, :, 10:13].count_nonzero())
@@ -357,4 +357,4 @@ def test_steps_without_n_q_are_not_disturbed(ctx):
     c2, e2 = enc.encode_slots(b, [3, 2], return_latent=True)
     y2 = dec.decode_slots(c2, [3, 2])
     assert torch.equal(c2, c1) and torch.equal(e2, e1) and torch.equal(y2, y1)
-    assert sorted(enc._s._slot_graphs) == [(3, False)] and sorted(enc0._s._slot_graphs) == [(3, False), (7, True)]
+    assert enc._s.graph_keys('slots') == [(3, False)] and enc0._s.graph_keys('slots') == [(3, False), (7, True)]

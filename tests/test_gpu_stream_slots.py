@@ -152,17 +152,17 @@ def test_unread_tail_may_hold_anything(ctx):
 
 def test_graph_equals_eager_and_one_graph_serves_both_joins(ctx):
     eager = Drive(ctx.m, [[c] for c in ctx.clips], graphs=False).steps(RUN1)
-    assert not eager.enc._s._slot_graphs and not eager.dec._s._slot_graphs
+    assert not eager.enc._s.graph_keys('slots') and not eager.dec._s.graph_keys('slots')
     d = Drive(ctx.m, [[c] for c in ctx.clips])
     d.steps(RUN1[:6])  # slot 1 joined in step 1: (n_max 7, a first chunk)
-    caught = [s._slot_graphs[(7, True)] for s in (d.enc._s, d.dec._s)]
-    keys = set(d.enc._s._slot_graphs)
+    caught = [s.graph('slots', (7, True)) for s in (d.enc._s, d.dec._s)]
+    keys = set(d.enc._s.graph_keys('slots'))
     d.steps(RUN1[6:])  # slot 2 joins in step 6
     for s, g in zip((d.enc._s, d.dec._s), caught):
-        assert s._slot_graphs[(7, True)] is g
-        assert sorted(s._slot_graphs) == sorted({(max(f), any(f[b] and not any(e[b] for e in RUN1[:i])
-                                                          for b in range(3))) for i, f in enumerate(RUN1)})
-    assert keys <= set(d.enc._s._slot_graphs)
+        assert s.graph('slots', (7, True)) is g
+        assert s.graph_keys('slots') == sorted({(max(f), any(f[b] and not any(e[b] for e in RUN1[:i])
+                                                             for b in range(3))) for i, f in enumerate(RUN1)})
+    assert keys <= set(d.enc._s.graph_keys('slots'))
     for b, (e, g) in enumerate(zip(eager.result(), d.result())):
         equal(g[0], e[0])
         equal(g[0], ctx.solo[b])  # both joins equal solo
@@ -280,3 +280,35 @@ def test_roll_skips_a_row_whose_count_would_leave_it():
     assert roll(2, [3, 0, 1, 1]) == 0                                     # zero: only the first-chunk slot
     want[C:2 * C, :P] = 0
     assert torch.equal(buf, want)
+
+
+@pytest.mark.parametrize('width', (2, 1))
+def test_device_table_uploads_on_change_through_rotating_staging(width):
+    """encx.slots.DeviceTable at B = 3: the same rows twice are one upload; nine different tables
+    (more than twice the four staging buffers) put back to back without a host synchronisation,
+    the device tensor cloned on the stream after each, all arrive as put; clear() zeroes the
+    table and the rows held before it upload again."""
+    from encx._lib import ensure_device
+    from encx.slots import DeviceTable
+    ensure_device(torch.device(DEV))
+    B = 3
+    rows = lambda i: tuple(10 * i + b if width == 1 else tuple(100 * i + 10 * b + w for w in range(width))
+                           for b in range(B))
+    t = DeviceTable(B, width, torch.device(DEV))
+    assert t.t.shape == ((B,) if width == 1 else (B, width)) and t.t.dtype == torch.int32
+    assert t.data_ptr() == t.t.data_ptr() and t.uploads == 0 and t.host is None
+    t.put(rows(0))
+    t.put(list(rows(0)))
+    assert t.uploads == 1 and t.host == rows(0)
+    clones = []
+    for i in range(1, 10):
+        t.put(rows(i))
+        clones.append(t.t.clone())
+    assert t.uploads == 10
+    torch.cuda.synchronize()
+    for i, c in enumerate(clones, 1):
+        assert torch.equal(c.cpu(), torch.tensor(rows(i), dtype=torch.int32)), i
+    t.clear()
+    assert t.host is None and not t.t.any().item()
+    t.put(rows(9))
+    assert t.uploads == 11 and torch.equal(t.t.cpu(), torch.tensor(rows(9), dtype=torch.int32))

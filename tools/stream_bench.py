@@ -202,7 +202,7 @@ def conceal_section(args, torch, m, dev, hop, timed, B=64, K=8):
             for k in ('eighth', 'all'):
                 row[f'{k}_over_none'] = round(row[k]['ms'] / row['none']['ms'], 4)
             row['none_spread'] = round((row['none']['max'] - row['none']['min']) / row['none']['ms'], 4)
-            row['conceal_graphs'] = len(dec._conceal_graphs)
+            row['conceal_graphs'] = len(dec._s.graph_keys('conceal'))
             rows.append(row)
             print(json.dumps(row), flush=True)
     return {'metric': f'ms per decode_slots step at B = {B} (graph replay), n_q {K}: none / one in eight / all of '
