@@ -48,6 +48,9 @@ ENCX_DEV uint64_t shfl_xor64(uint64_t v, int o) {
 // k-steps; its 4 waves are 2 x 2 tiles of 32 x 32. 66 KB of LDS: two workgroups per CU, so one
 // hides the other's LDS and load latency (at 128 codes, 100 KB, one per CU: MFMA busy 0.08).
 // 38 x 16 = 608 workgroups at N = 2400.
+// The reduction runs two d per MFMA step (half-wave h takes d = dp + h), so an odd D is staged with
+// one more row of zeros at d = D (Dp = D rounded up to even): the last step adds 0 * 0. |x|^2 and
+// |e|^2 run over D.
 constexpr int AR_ROWS = 64, AR_CODES = 64, AR_BS = AR_CODES + 1;
 constexpr int AR_PER = 8;    // staging loads in flight per thread (scalar code path)
 constexpr int AR_XPER = 32;  // frame-element loads in flight per thread
@@ -56,9 +59,10 @@ constexpr int AR_EPER = 16;  // code quads in flight per thread
 __global__ __launch_bounds__(NT) void rvq_argmin_mfma(Rows x, const float* embed, uint64_t* keys,
                                                       int N, int D, int Kc) {
     extern __shared__ float sm[];
-    float* As = sm;                        // [D][AR_ROWS]
-    float* Bs = As + D * AR_ROWS;          // [D][AR_BS]
-    float* xx = Bs + D * AR_BS;            // [AR_ROWS]
+    const int Dp = D + (D & 1);
+    float* As = sm;                        // [Dp][AR_ROWS]
+    float* Bs = As + Dp * AR_ROWS;         // [Dp][AR_BS]
+    float* xx = Bs + Dp * AR_BS;           // [AR_ROWS]
     float* ee = xx + AR_ROWS;              // [AR_CODES]
     __shared__ uint64_t part[2][AR_ROWS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -130,6 +134,10 @@ __global__ __launch_bounds__(NT) void rvq_argmin_mfma(Rows x, const float* embed
             if (i < AR_CODES * D) Bs[d * AR_BS + c] = v[q];
         }
     }
+    if (D & 1) {  // the zero row of an odd D
+        if (tid < AR_ROWS) As[D * AR_ROWS + tid] = 0.f;
+        else if (tid < AR_ROWS + AR_BS) Bs[D * AR_BS + tid - AR_ROWS] = 0.f;
+    }
     __syncthreads();
     // |x|^2 and |e|^2 in ascending d (fmaf chain)
     if (tid < AR_ROWS) {
@@ -198,6 +206,57 @@ __global__ __launch_bounds__(NT) void rvq_argmin_direct(Rows x, const float* emb
             float df = xs[r * D + d] - es[tid * (D + 1) + d];
             s = fmaf(df, df, s);
         }
+        uint64_t key = k < Kc ? (((uint64_t)ord_key(s) << 32) | (uint32_t)k) : ~0ull;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) key = umin64(key, shfl_xor64(key, o));
+        if (lane == 0) part[wave] = key;
+        __syncthreads();
+        if (tid == 0 && n0 + r < N) {
+            uint64_t b = umin64(umin64(part[0], part[1]), umin64(part[2], part[3]));
+            atomicMin((unsigned long long*)&keys[n0 + r], (unsigned long long)b);
+        }
+        __syncthreads();
+    }
+}
+
+// rvq_argmin_direct for a D whose whole-D tile does not fit the LDS (D > 141): the codes are staged
+// DC_D dims at a time and each (row, code) sum is carried from chunk to chunk in LDS (a thread reads
+// and writes only its own), so a distance is still ONE fmaf chain of (x - e)^2 in ascending d.
+constexpr int DC_D = 64;
+
+__global__ __launch_bounds__(NT) void rvq_argmin_direct_chunked(Rows x, const float* embed, uint64_t* keys,
+                                                                int N, int D, int Kc) {
+    extern __shared__ float sm[];
+    float* es = sm;                        // [256][DC_D+1]
+    float* xs = es + NT * (DC_D + 1);      // [DR_ROWS][D]
+    float* acc = xs + DR_ROWS * D;         // [DR_ROWS][256]
+    __shared__ uint64_t part[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n0 = blockIdx.x * DR_ROWS, k = blockIdx.y * NT + tid;
+    for (int i = tid; i < DR_ROWS * D; i += NT) {
+        int r = i / D, d = i - r * D;
+        xs[i] = (n0 + r < N) ? x.at(n0 + r, d) : 0.f;
+    }
+    for (int r = 0; r < DR_ROWS; ++r) acc[r * NT + tid] = 0.f;
+    for (int d0 = 0; d0 < D; d0 += DC_D) {
+        const int dc = D - d0 < DC_D ? D - d0 : DC_D;
+        __syncthreads();  // the previous chunk's codes are read (first round: xs visible)
+        for (int i = tid; i < NT * dc; i += NT) {
+            int c = i / dc, d = i - c * dc, kk = blockIdx.y * NT + c;
+            es[c * (DC_D + 1) + d] = kk < Kc ? embed[(int64_t)kk * D + d0 + d] : 0.f;
+        }
+        __syncthreads();
+        for (int r = 0; r < DR_ROWS; ++r) {
+            float s = acc[r * NT + tid];
+            for (int d = 0; d < dc; ++d) {
+                float df = xs[r * D + d0 + d] - es[tid * (DC_D + 1) + d];
+                s = fmaf(df, df, s);
+            }
+            acc[r * NT + tid] = s;
+        }
+    }
+    for (int r = 0; r < DR_ROWS; ++r) {
+        const float s = acc[r * NT + tid];
         uint64_t key = k < Kc ? (((uint64_t)ord_key(s) << 32) | (uint32_t)k) : ~0ull;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) key = umin64(key, shfl_xor64(key, o));
@@ -339,6 +398,8 @@ __global__ void ema_from_sums(const float* sums, int D, float* cs, float* ea, fl
 }
 
 // embed = embed_avg / (laplace(cluster_size) * sum(cluster_size)), core_vq.py:230-235
+// block_sum needs whole waves: the block is D rounded up to a multiple of 64 (64..256)
+int ema_normalize_threads(int64_t D) { return D > 192 ? 256 : (D <= 64 ? 64 : (int)((D + 63) / 64 * 64)); }
 __global__ void ema_normalize(const float* cs, const float* ea, float* embed, int D, int Kc,
                               float eps, float keps) {
     __shared__ float red[16];
@@ -394,15 +455,21 @@ int argmin_run(Rows x, const float* embed, int64_t* idx, uint64_t* keys, int N, 
                int direct, hipStream_t st) {
     hipLaunchKernelGGL(fill_u64, dim3(cdiv(N, 256)), dim3(256), 0, st, keys, ~0ull, N);
     if (!direct) {
-        const size_t lds = (size_t)(D * (AR_ROWS + AR_BS) + AR_ROWS + AR_CODES) * sizeof(float);
-        if (lds > 150 * 1024) return ENCX_EINVAL;
+        const size_t lds = (size_t)((D + (D & 1)) * (AR_ROWS + AR_BS) + AR_ROWS + AR_CODES) * sizeof(float);
+        if (lds > 150 * 1024) return ENCX_EINVAL;  // D <= 256: 130 KB
         hipLaunchKernelGGL(rvq_argmin_mfma, dim3(cdiv(N, AR_ROWS), cdiv(Kc, AR_CODES)), dim3(NT), lds,
                            st, x, embed, keys, N, D, Kc);
     } else {
         size_t lds = (size_t)(NT * (D + 1) + DR_ROWS * D) * sizeof(float);
-        if (lds > 160 * 1024) return ENCX_EINVAL;
-        hipLaunchKernelGGL(rvq_argmin_direct, dim3(cdiv(N, DR_ROWS), cdiv(Kc, NT)), dim3(NT), lds, st,
-                           x, embed, keys, N, D, Kc);
+        if (lds <= 160 * 1024) {
+            hipLaunchKernelGGL(rvq_argmin_direct, dim3(cdiv(N, DR_ROWS), cdiv(Kc, NT)), dim3(NT), lds, st,
+                               x, embed, keys, N, D, Kc);
+        } else {  // D > 141
+            lds = (size_t)(NT * (DC_D + 1) + DR_ROWS * D + DR_ROWS * NT) * sizeof(float);
+            if (lds > 160 * 1024) return ENCX_EINVAL;  // D <= 256: 129 KB
+            hipLaunchKernelGGL(rvq_argmin_direct_chunked, dim3(cdiv(N, DR_ROWS), cdiv(Kc, NT)), dim3(NT), lds,
+                               st, x, embed, keys, N, D, Kc);
+        }
     }
     ENCX_CHECK_LAUNCH();
     hipLaunchKernelGGL(keys_to_idx, dim3(cdiv(N, 256)), dim3(256), 0, st, keys, idx, N);
@@ -468,7 +535,7 @@ int encx_rvq_ema(const float* x, const int64_t* idx, float* cluster_size, float*
     int rc = bucket_run<0>(bdt_rows(x, B, D, Tf), idx, (int)(B * Tf), (int)D, (int)Kc, ws,
                            cluster_size, embed_avg, nullptr, nullptr, decay, one_m, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(ema_normalize, dim3(Kc), dim3(D < 64 ? 64 : (D > 256 ? 256 : D)), 0, st,
+    hipLaunchKernelGGL(ema_normalize, dim3(Kc), dim3(ema_normalize_threads(D)), 0, st,
                        cluster_size, embed_avg, embed, (int)D, (int)Kc, eps,
                        (float)((double)Kc * (double)eps));
     ENCX_CHECK_LAUNCH();
@@ -490,7 +557,7 @@ int encx_rvq_ema_from_sums(const float* sums, float* cluster_size, float* embed_
     hipLaunchKernelGGL(ema_from_sums, dim3(Kc), dim3(D + 1 < 64 ? 64 : 256), 0, st, sums, (int)D,
                        cluster_size, embed_avg, decay, one_m);
     ENCX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ema_normalize, dim3(Kc), dim3(D < 64 ? 64 : (D > 256 ? 256 : D)), 0, st,
+    hipLaunchKernelGGL(ema_normalize, dim3(Kc), dim3(ema_normalize_threads(D)), 0, st,
                        cluster_size, embed_avg, embed, (int)D, (int)Kc, eps,
                        (float)((double)Kc * (double)eps));
     ENCX_CHECK_LAUNCH();

@@ -223,7 +223,11 @@ int encx_l1_loss(const float* x, const float* y, float* loss, float* grad, float
  * core_vq.py:303; the kernels index it in place). N = B*Tf frames.
  * Nearest code, EuclideanCodebook.quantize (core_vq.py:181-189): idx[n] = argmax_k
  * -((|x_n|^2 - 2 x_n.e_k) + |e_k|^2), first index on ties. direct != 0 selects kmeans' form
- * -sum_d (x_n,d - e_k,d)^2 (core_vq.py:86-89). keys: workspace of N uint64. */
+ * -sum_d (x_n,d - e_k,d)^2 (core_vq.py:86-89). keys: workspace of N uint64.
+ * Both forms take every 1 <= D <= 256 (odd D included) and any Kc >= 1; ENCX_EINVAL outside. The
+ * first stages the whole D of 64 frames and 64 codes (an odd D with a row of zeros); the direct form
+ * stages the whole D up to 141 and 64 dims at a time above, each distance one ascending-d chain
+ * either way. */
 int encx_rvq_argmin(const float* res, const float* embed, int64_t* idx, uint64_t* keys,
                     int64_t B, int64_t D, int64_t Tf, int64_t Kc, int direct,
                     encx_stream_t stream);
@@ -260,7 +264,9 @@ int encx_rvq_code_sums(const float* x, const int64_t* idx, float* sums, float* w
 int encx_rvq_ema_from_sums(const float* sums, float* cluster_size, float* embed_avg, float* embed,
                            int64_t D, int64_t Kc, float decay, float eps, encx_stream_t stream);
 /* One kmeans iteration (core_vq.py:85-100): means <- bucket means where bins > 0.
- * samples [N][D] row-major; means [Kc][D] in/out; bins int64 [Kc] out; ws as above. */
+ * samples [N][D] row-major; means [Kc][D] in/out; bins int64 [Kc] out; ws as above.
+ * 1 <= D <= 256 (the direct form of encx_rvq_argmin), any Kc >= 1; the mean of an empty cluster
+ * is left as it is. */
 int encx_kmeans_step(const float* samples, float* means, int64_t* bins, int64_t* idx,
                      uint64_t* keys, float* ws, int64_t N, int64_t D, int64_t Kc,
                      encx_stream_t stream);

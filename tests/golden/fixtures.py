@@ -134,13 +134,49 @@ def rvq_certified(emb, embeds, factor=256):
     return torch.stack(codes), torch.stack(certs)
 
 
+# The g15 fixture's RVQ shapes (dimension, bins), both n_q 2 on a [2, D, 50] latent, and its kmeans run.
+G15_RVQ = {'a': (40, 100), 'b': (96, 300)}
+G15_KM = dict(N=200, D=40, clusters=30, iters=5)
+
+
+def g15_inputs(name):
+    """-> (emb [2, D, 50], gq, codebooks) of g15_rvq_shapes.npz's case `name`: seeded standard-normal
+    draws, the second layer's codebook at 0.6 of the first's scale (about a residual's)."""
+    D, bins = G15_RVQ[name]
+    g = rng(1500 + ord(name))
+    emb = g.standard_normal((2, D, 50)).astype(np.float32)
+    gq = g.standard_normal((2, D, 50)).astype(np.float32)
+    cbs = []
+    for i in range(2):
+        E = ((1.0, 0.6)[i] * g.standard_normal((bins, D))).astype(np.float32)
+        cs = g.uniform(0.0, 4.0, size=(bins,)).astype(np.float32)
+        ea = g.standard_normal((bins, D)).astype(np.float32)
+        cbs.append({'inited': torch.ones(1), 'cluster_size': T(cs), 'embed': T(E), 'embed_avg': T(ea)})
+    return T(emb), T(gq), cbs
+
+
+def g15_rows(codes, bins):
+    """The codebook rows g15 stores of a layer's updated embed / embed_avg: every row a frame was
+    assigned to and every fifth of the others (those only decay)."""
+    return np.union1d(np.unique(np.asarray(codes).reshape(-1)), np.arange(0, bins, 5)).astype(np.int64)
+
+
+def g15_kmeans_inputs():
+    """-> (samples [N, D], init indices [clusters]) of g15's kmeans run."""
+    k = G15_KM
+    g = rng(1515)
+    samples = g.standard_normal((k['N'], k['D'])).astype(np.float32)
+    init = g.permutation(k['N'])[:k['clusters']].astype(np.int64)
+    return T(samples), T(init)
+
+
 def g13_samples(n, count=64):
     """The evenly spaced element indices of an n-element tensor that g13_ddp.npz stores."""
     return np.unique(np.linspace(0, n - 1, min(n, count)).round().astype(np.int64))
 
 
 __all__ = ['load', 'g13_samples', 'T', 'model_state', 'disc_state', 'cfg48k', 'arch_cfg', 'arch_modules', 'ARCHS',
-           'codebooks_from_stats', 'g3_codebooks',
+           'codebooks_from_stats', 'g3_codebooks', 'G15_RVQ', 'G15_KM', 'g15_inputs', 'g15_rows', 'g15_kmeans_inputs',
            'certified', 'rvq_certified', 'synth_wave', 'rng']
 
 

@@ -26,6 +26,8 @@ Fixture map:
   g14_seanet_arch.npz  SEANetEncoder -> SEANetDecoder of three non-default architectures
                    (fixtures.ARCHS: n_residual_layers 2-3 with dilations, true_skip, compress 4,
                    other kernel sizes / ratios / widths, lstm 0 / 1 / 3), forward + all grads
+  g15_rvq_shapes.npz  RVQ train forward at (dimension 40, bins 100) and (96, 300), n_q 2: codes,
+                   quantized, penalty, emb grad, updated buffers; kmeans at N 200, D 40, 30 clusters
 """
 import os
 import sys
@@ -893,8 +895,47 @@ def g14():
     save('g14_seanet_arch.npz', **out)
 
 
+# ------------------------------------------------------------------------------------ G15
+def g15():
+    """The reference's ResidualVectorQuantizer in train mode at codebook shapes other than 1024 x 128
+    (fixtures.G15_RVQ), and one kmeans run at D 40. Inputs are rebuilt from seeds (fixtures.g15_inputs);
+    of the updated embed / embed_avg the rows fixtures.g15_rows names are stored."""
+    from fixtures import G15_RVQ, G15_KM, g15_inputs, g15_rows, g15_kmeans_inputs
+    outs = {}
+    for name in sorted(G15_RVQ):
+        D, bins = G15_RVQ[name]
+        q = R.quantization.ResidualVectorQuantizer(dimension=D, n_q=2, bins=bins)
+        emb, gq, cbs = g15_inputs(name)
+        for layer, cb in zip(q.vq.layers, cbs):
+            c = layer._codebook
+            for k in ('embed', 'cluster_size', 'embed_avg'):
+                getattr(c, k).data.copy_(cb[k])
+            c.inited.data.fill_(1.0)
+        q.train()
+        x = emb.clone().requires_grad_(True)
+        res = q(x, 50)
+        torch.autograd.backward([res.quantized, res.penalty], [gq, torch.tensor(1.0)])
+        outs.update({f'{name}/codes': res.codes.numpy().astype(np.int16),
+                     f'{name}/quantized': res.quantized.detach().numpy(),
+                     f'{name}/penalty': res.penalty.detach().numpy(), f'{name}/demb': x.grad.numpy(),
+                     f'{name}/gaps': top2_gaps(emb, [cb['embed'] for cb in cbs], res.codes)})
+        for i, layer in enumerate(q.vq.layers):
+            c = layer._codebook
+            rows = g15_rows(res.codes[i], bins)
+            outs[f'{name}/cluster_size{i}'] = c.cluster_size.numpy()
+            outs[f'{name}/embed_avg{i}'] = c.embed_avg.numpy()[rows]
+            outs[f'{name}/embed{i}'] = c.embed.numpy()[rows]
+    samples, init_idx = g15_kmeans_inputs()
+    orig = R.quantization.core_vq.sample_vectors
+    R.quantization.core_vq.sample_vectors = lambda s, n: s[init_idx]
+    means, bins = R.quantization.core_vq.kmeans(samples, G15_KM['clusters'], G15_KM['iters'])
+    R.quantization.core_vq.sample_vectors = orig
+    outs.update(km_means=means.numpy(), km_bins=bins.numpy())
+    save('g15_rvq_shapes.npz', **outs)
+
+
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['g1', 'g2', 'g3', 'g4', 'g5', 'g6', 'g7', 'g8', 'g9', 'g10', 'g11', 'g12', 'g13', 'g14']
+    which = sys.argv[1:] or ['g1', 'g2', 'g3', 'g4', 'g5', 'g6', 'g7', 'g8', 'g9', 'g10', 'g11', 'g12', 'g13', 'g14', 'g15']
     for w in which:
         torch.manual_seed(0)
         globals()[w]()

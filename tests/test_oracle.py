@@ -142,6 +142,51 @@ def test_oracle_kmeans_fixture():
     assert (bins.numpy() == d['km_bins']).all()
 
 
+@pytest.mark.parametrize('name', ['a', 'b'])
+def test_oracle_rvq_train_other_shapes_fixture(name):
+    """O.rvq_train / O.codebook_ema at (dimension 40, bins 100) and (96, 300) against the reference's
+    ResidualVectorQuantizer (g15), at the G3 tolerances: the oracle the GPU shape tests lean on is
+    tied to the reference away from 128 x 1024 too."""
+    from fixtures import G15_RVQ, g15_inputs, g15_rows
+    d = load('g15_rvq_shapes.npz')
+    D, bins = G15_RVQ[name]
+    emb, gq, cbs = g15_inputs(name)
+    assert emb.shape == (2, D, 50) and cbs[0]['embed'].shape == (bins, D)
+    emb = emb.clone().requires_grad_(True)
+    q, codes, penalty, new = O.rvq_train(emb, cbs, 2)
+    assert (codes.numpy() == d[f'{name}/codes']).all()
+    close(q, d[f'{name}/quantized'])
+    close(penalty, d[f'{name}/penalty'])
+    torch.autograd.backward([q, penalty], [gq, torch.tensor(1.0)])
+    close(emb.grad, d[f'{name}/demb'], rtol=1e-5, atol=1e-6)
+    x = emb.detach().permute(0, 2, 1).reshape(-1, D)
+    for i in range(2):
+        rows = g15_rows(d[f'{name}/codes'][i], bins)
+        assert len(rows) < bins  # a code no frame took is among the rows left out: they only decay
+        close(new[i]['cluster_size'], d[f'{name}/cluster_size{i}'], rtol=1e-6, atol=1e-7)
+        close(new[i]['embed_avg'][rows], d[f'{name}/embed_avg{i}'], rtol=1e-5, atol=1e-6)
+        close(new[i]['embed'][rows], d[f'{name}/embed{i}'], rtol=1e-5, atol=1e-6)
+        # the EMA on its own, from the reference's codes and this layer's input
+        ema = O.codebook_ema(x, T(d[f'{name}/codes'][i].astype(np.int64)).reshape(-1), cbs[i])
+        close(ema['cluster_size'], d[f'{name}/cluster_size{i}'], rtol=1e-6, atol=1e-7)
+        close(ema['embed_avg'][rows], d[f'{name}/embed_avg{i}'], rtol=1e-5, atol=1e-6)
+        close(ema['embed'][rows], d[f'{name}/embed{i}'], rtol=1e-5, atol=1e-6)
+        x = x - cbs[i]['embed'][T(d[f'{name}/codes'][i].astype(np.int64)).reshape(-1)]
+
+
+def test_oracle_kmeans_other_shape_fixture():
+    from fixtures import G15_KM, g15_kmeans_inputs
+    d = load('g15_rvq_shapes.npz')
+    samples, init = g15_kmeans_inputs()
+    means, bins = O.kmeans(samples, G15_KM['clusters'], G15_KM['iters'], init)
+    close(means, d['km_means'], rtol=1e-5, atol=1e-6)
+    assert (bins.numpy() == d['km_bins']).all()
+    # started from given means, a step is the same step
+    m1, _ = O.kmeans(samples, G15_KM['clusters'], 1, init)
+    m2, b2 = O.kmeans(samples, G15_KM['clusters'], G15_KM['iters'] - 1, None, means=m1)
+    assert torch.equal(m2, means) and torch.equal(b2, bins)
+
+
 # --------------------------------------------------------------------------- G4 mel
 def test_oracle_mel_and_spec_fixture():
     d = load('g4_mel.npz')
