@@ -612,6 +612,28 @@ int lm_linear(const float* x, int ldx, const float* w, int ldw, int M, int N, in
     return gemm_launch(LdRows{x, w, ldx, ldw}, ep, M, N, K, st);
 }
 
+// One launch of lm_attn_row_kernel<HD, SLOTS> with `lds` bytes of dynamic LDS. A window near
+// past_context 1000, or head dims above 32 from a window of ~260, need more than the default
+// dynamic LDS limit of 64 KB: the limit is raised per kernel function whenever a launch asks for
+// more than was raised for that function (by the eager step that precedes any capture, which has
+// the capture's own size), not on every launch.
+template <int HD, bool SLOTS>
+int lm_attn_row_launch(size_t lds, const float* q, const float* kv, const float* in_b, float* ctx, int64_t rows, int T,
+                       int D, int H, int64_t L, int64_t seq0, const int64_t* dstep, int64_t P, const SlotRows& sr,
+                       hipStream_t st) {
+    static size_t raised = 64 * 1024;
+    if (lds > raised) {
+        const hipError_t e = hipFuncSetAttribute((const void*)lm_attn_row_kernel<HD, SLOTS>,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+        raised = lds;
+    }
+    hipLaunchKernelGGL((lm_attn_row_kernel<HD, SLOTS>), dim3((unsigned)(rows * H)), dim3(256), lds, st, q, kv, in_b,
+                       ctx, T, D, H, L, seq0, dstep, P, sr);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
+
 }  // namespace
 
 // ---- softmax over the codebook + quantized CDF (ac.hip), shared with the coder entry points
@@ -687,34 +709,15 @@ int lm_layer_run(const float* x, float* y, int64_t B, int64_t T, float* kv, int6
     const int64_t win = (P + 1 < seq0 + T || dev_step || sr) ? P + 1 : seq0 + T;
     const int hd = (int)(D / heads);
     ENCX_REQUIRE(N * heads <= INT32_MAX);
-    if (sr) {  // a step has at most 64 slots x 255 frames; the row kernel serves them all
+    // a slots step has at most 64 slots x 255 frames; the row kernel serves them all
+    if (sr || N * heads <= 4096 || dev_step) {
         const size_t lds = (size_t)win * (hd + 1) * sizeof(float);
         ENCX_REQUIRE(lds <= 150 * 1024);
-        // a past_context near 1000 needs more than the default dynamic LDS limit: raised once per
-        // size (by the eager step that precedes any capture), not on every launch
-        static size_t raised[2] = {64 * 1024, 64 * 1024};
-        if (lds > raised[hd > 32]) {
-            const void* fn = hd <= 32 ? (const void*)lm_attn_row_kernel<32, true>
-                                      : (const void*)lm_attn_row_kernel<64, true>;
-            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-            raised[hd > 32] = lds;
-        }
-        if (hd <= 32)
-            hipLaunchKernelGGL((lm_attn_row_kernel<32, true>), dim3((unsigned)(N * heads)), dim3(256), lds, st, q, kv,
-                               in_b, ctx, (int)T, d, (int)heads, L, seq0, dev_step, P, *sr);
-        else
-            hipLaunchKernelGGL((lm_attn_row_kernel<64, true>), dim3((unsigned)(N * heads)), dim3(256), lds, st, q, kv,
-                               in_b, ctx, (int)T, d, (int)heads, L, seq0, dev_step, P, *sr);
-    } else if (N * heads <= 4096 || dev_step) {
-        const size_t lds = (size_t)win * (hd + 1) * sizeof(float);
-        ENCX_REQUIRE(lds <= 150 * 1024);
-        if (hd <= 32)
-            hipLaunchKernelGGL((lm_attn_row_kernel<32, false>), dim3((unsigned)(N * heads)), dim3(256), lds, st, q, kv,
-                               in_b, ctx, (int)T, d, (int)heads, L, seq0, dev_step, P, SlotRows{});
-        else
-            hipLaunchKernelGGL((lm_attn_row_kernel<64, false>), dim3((unsigned)(N * heads)), dim3(256), lds, st, q, kv,
-                               in_b, ctx, (int)T, d, (int)heads, L, seq0, dev_step, P, SlotRows{});
+        const SlotRows rows = sr ? *sr : SlotRows{};
+        auto launch = sr ? (hd <= 32 ? lm_attn_row_launch<32, true> : lm_attn_row_launch<64, true>)
+                         : (hd <= 32 ? lm_attn_row_launch<32, false> : lm_attn_row_launch<64, false>);
+        rc = launch(lds, q, kv, in_b, ctx, N, (int)T, d, (int)heads, L, seq0, dev_step, P, rows, st);
+        if (rc) return rc;
     } else {
         const int tblocks = (int)cdiv(T, 64);
         const int64_t nw = B * heads * tblocks;

@@ -40,6 +40,23 @@ TOTAL_RANGE_BITS = 24   # ArithmeticCoder default (ac.py:96), as compress.py use
 ROUNDOFF = 1e-8         # build_stable_quantized_cdf defaults (ac.py:18-20)
 MIN_RANGE = 2
 
+# The limits of csrc/lm.hip. The reference builds an LM of any size; these are this port's.
+MAX_DIM = 512           # LayerNorm holds a row in one wave, 8 values per lane
+MAX_HEAD_DIM = 64       # the attention kernels' widest instantiation
+MAX_CARD = 65536        # encx_lm_heads
+MAX_CODEBOOKS = 64      # the input stage fetches one index per lane
+MAX_ATTN_LDS = 150 * 1024   # the few-row attention kernel keeps its window's weights and values in LDS
+
+
+def _check_window(tr, rows):
+    """The few-row attention kernel holds `rows` key positions x (1 + head dim) floats in LDS."""
+    hd = tr.dim // tr.num_heads
+    need = rows * (hd + 1) * 4
+    if need > MAX_ATTN_LDS:
+        raise ValueError(f'encx LM: an attention window of {rows} positions at head dim {hd} needs {need} bytes of '
+                         f'LDS, above this port\'s limit of {MAX_ATTN_LDS} (the reference has none): past_context '
+                         f'{tr.past_context} is too long for dim {tr.dim} with {tr.num_heads} heads')
+
 
 class StreamingTransformerEncoderLayer(nn.Module):
     """Parameter holder with nn.TransformerEncoderLayer's names (transformer.py:30)."""
@@ -60,7 +77,14 @@ class StreamingTransformerEncoder(nn.Module):
                  max_period: float = 10000, past_context: int = 1000, gelu: bool = True,
                  norm_in: bool = True, dropout: float = 0., **kwargs):
         super().__init__()
+        if dim < 4 or dim > MAX_DIM or dim % 2:
+            raise ValueError(f'encx LM: dim {dim}; this port takes an even dim in 4..{MAX_DIM} (the reference any)')
         assert dim % num_heads == 0
+        if dim // num_heads > MAX_HEAD_DIM:
+            raise ValueError(f'encx LM: head dim {dim // num_heads} (dim {dim} / {num_heads} heads); this port takes '
+                             f'head dims up to {MAX_HEAD_DIM} (the reference any)')
+        if past_context < 0:
+            raise ValueError(f'encx LM: past_context {past_context} is negative')
         if not gelu or not norm_in or dropout or kwargs:
             raise NotImplementedError('encx LM: GELU, norm_in and dropout 0 only (the configuration '
                                       'EncodecModel.get_lm_model builds, model.py:224-225)')
@@ -223,6 +247,8 @@ class LMModel(nn.Module):
 
     def __init__(self, n_q: int = 32, card: int = 1024, dim: int = 200, **kwargs):
         super().__init__()
+        if not 1 <= card <= MAX_CARD:
+            raise ValueError(f'encx LM: card {card}; this port takes 1..{MAX_CARD} (the reference any)')
         self.card = card
         self.n_q = n_q
         self.dim = dim
@@ -262,6 +288,13 @@ class LMModel(nn.Module):
             if not t.is_contiguous():
                 raise RuntimeError('encx LM: parameters must be contiguous')
 
+    def _check_codebooks(self, K):
+        if K > self.n_q:
+            raise ValueError(f'{K} codebooks for an LM of n_q={self.n_q}')
+        if not 1 <= K <= MAX_CODEBOOKS:
+            raise ValueError(f'encx LM: {K} codebooks in one call; this port takes 1..{MAX_CODEBOOKS} '
+                             '(the reference any)')
+
     def new_state(self, B, capacity=64):
         tr = self.transformer
         return LMState(B, len(tr.layers), self.dim, max(int(capacity), 2), self._emb.device)
@@ -276,6 +309,12 @@ class LMModel(nn.Module):
         dev = self._emb.device
         st = stream()
         dptr = dev_step.data_ptr() if dev_step is not None else None
+        # the few-row attention kernel (csrc/lm.hip lm_layer_run): its window is sized for the whole
+        # past_context when the step is read on the device
+        if dev_step is not None:
+            _check_window(tr, tr.past_context + 1)
+        elif B * T * tr.num_heads <= 4096:
+            _check_window(tr, min(tr.past_context + 1, state.offset + 1 + T))
         if dev_step is None:
             state.reserve(state.offset + T + 1)
         x = torch.empty(B * T, D, device=dev)
@@ -342,8 +381,7 @@ class LMModel(nn.Module):
         if codes.device != self._emb.device:
             raise RuntimeError(f'encx LM: codes on {codes.device}, parameters on {self._emb.device}')
         B, K, T = codes.shape
-        if K > self.n_q:
-            raise ValueError(f'{K} codebooks for an LM of n_q={self.n_q}')
+        self._check_codebooks(K)
         if B < 1 or T < 1:
             raise ValueError('encx LM: nll needs at least one code')
         # the input stage reads the embedding table at the code: check before any launch
@@ -361,8 +399,7 @@ class LMModel(nn.Module):
         if indices.dtype != torch.int64 or indices.dim() != 3 or not indices.is_cuda:
             raise RuntimeError('encx LM: indices must be int64 [B, K, T] on the GPU')
         B, K, T = indices.shape
-        if K > self.n_q:
-            raise ValueError(f'{K} codebooks for an LM of n_q={self.n_q}')
+        self._check_codebooks(K)
         if states is None:
             states = self.new_state(B, T + 1)
             states.offset = int(offset)
@@ -386,8 +423,7 @@ class LMModel(nn.Module):
         if codes.dtype != torch.int64 or codes.dim() != 3 or not codes.is_cuda:
             raise RuntimeError('encx LM: codes must be int64 [B, K, T] on the GPU')
         B, K, T = codes.shape
-        if K > self.n_q:
-            raise ValueError(f'{K} codebooks for an LM of n_q={self.n_q}')
+        self._check_codebooks(K)
         dev = codes.device
         state = self.new_state(B, T + 1)
         x = self._body(codes, codes.stride(), B, K, T, True, state)
@@ -426,8 +462,7 @@ class LMModel(nn.Module):
         file's segments are decoded from one upload of the file."""
         self._packed()
         self._check_device()
-        if K > self.n_q:
-            raise ValueError(f'{K} codebooks for an LM of n_q={self.n_q}')
+        self._check_codebooks(K)
         dev = self._emb.device
         if dev_span is not None:
             src, off, count = dev_span
@@ -507,6 +542,7 @@ class _LMSlots:
             raise ValueError(f'encx LM streaming: {K} codebooks for an LM of n_q={lm.n_q} (at most 64)')
         if not 1 <= max_frames <= MAX_PACKET_FRAMES:
             raise ValueError(f'encx LM streaming: max_frames {max_frames} (1..{MAX_PACKET_FRAMES})')
+        _check_window(lm.transformer, int(lm.transformer.past_context) + 1)
         self.lm, self.B, self.K = lm, int(batch), int(K)
         self.max_frames, self.graphs = int(max_frames), bool(graphs)
         self.R = int(lm.transformer.past_context) + self.max_frames
