@@ -10,6 +10,8 @@
 // The slots of a streaming step deliver unequal frame counts: encx_bitpack_slots /
 // encx_bitunpack_slots handle them in one launch too, each slot's count read from the device
 // slot table, one packet (header byte + payload) per slot (encx.h: the packet format).
+// encx_bitpack_slots_fec adds, in the same launch, a copy of the first codebooks of each slot's
+// previous packet from a history it keeps on the device (encx.h: REDUNDANT PACKET).
 #include "common.h"
 #include "prof.h"
 
@@ -174,6 +176,77 @@ __global__ void bitpack_slots_kernel(const int64_t* __restrict__ codes, int64_t 
     if (bad) atomicOr(err, 1);
 }
 
+// A slot's row of the fec table (encx.h: fec[B][4]), clamped: the copy's frames 0..h_max and
+// codebooks 0..R, both 0 when either is, and the copy of the history that holds the slot's
+// previous packet (this launch writes the other one).
+struct fec_row {
+    int n_r, K_r, par;
+};
+ENCX_DEV fec_row slot_fec(const int32_t* fec, int b, int h_max, int R) {
+    int n = fec[4 * b], q = fec[4 * b + 1];
+    n = n < 0 ? 0 : (n > h_max ? h_max : n);
+    q = q < 0 ? 0 : (q > R ? R : q);
+    if (!n || !q) n = q = 0;
+    return {n, q, fec[4 * b + 2] & 1};
+}
+
+// One redundant packet per slot (encx.h: REDUNDANT PACKET). Slot b has gm lanes for its main
+// section, which pack as bitpack_slots_kernel<true> behind a four-byte header, and gr lanes for
+// the copy of its previous packet: lane g of those packs codes 8g..8g+7 of the K_r x n_r grid
+// kept in hist[par] at the first byte after the main section. A main lane also keeps what it
+// packed: the codes of rows k < min(R, K_b) go to hist[par ^ 1]. The two copies are disjoint,
+// so no lane reads a cell this launch writes; the host flips par only when the slot delivered
+// and no code was refused. A slot that sits out writes nothing, neither packet nor history.
+__global__ void bitpack_slots_fec_kernel(const int64_t* __restrict__ codes, int64_t s_b, int64_t s_k, int64_t s_t,
+                                         int B, int K, int n_max, int bits, int R, int h_max,
+                                         const int32_t* __restrict__ slots, const int32_t* __restrict__ nq,
+                                         const int32_t* __restrict__ fec, int64_t* hist,
+                                         uint8_t* __restrict__ out, int64_t out_stride,
+                                         int64_t* __restrict__ nbytes, int gm, int gr, int* __restrict__ err) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= B * (gm + gr)) return;
+    const int b = j / (gm + gr), g = j - b * (gm + gr);
+    const int Kb = slot_nq(nq, b, K);
+    const int frames = Kb ? slot_frames(slots, b, n_max) : 0;
+    if (!frames) {
+        if (g == 0) nbytes[b] = 0;
+        return;
+    }
+    const fec_row f = slot_fec(fec, b, h_max, R);
+    const int n = frames * Kb, nr = f.n_r * f.K_r;
+    const int64_t main_bytes = ((int64_t)n * bits + 7) / 8;
+    uint8_t* pkt = out + b * out_stride;
+    const int64_t plane = (int64_t)B * R * h_max;  // one copy of the history, [B][R][h_max]
+    const int64_t row0 = (int64_t)b * R * h_max;
+    uint64_t bad = 0;
+    if (g < gm) {
+        if (g == 0) {
+            nbytes[b] = 4 + main_bytes + ((int64_t)nr * bits + 7) / 8;
+            pkt[0] = (uint8_t)frames;
+            pkt[1] = (uint8_t)Kb;
+            pkt[2] = (uint8_t)f.n_r;
+            pkt[3] = (uint8_t)f.K_r;
+        }
+        const int v0 = g * 8;
+        if (v0 >= n) return;
+        const int cnt = n - v0 < 8 ? n - v0 : 8;
+        const int64_t* src = codes + b * s_b;
+        bad = pack_group(src, s_k, s_t, Kb, v0, cnt, bits, pkt + 4 + (int64_t)g * bits);
+        int64_t* keep = hist + (f.par ^ 1) * plane + row0;
+        int t = v0 / Kb, k = v0 - t * Kb;
+        for (int i = 0; i < cnt; ++i) {
+            if (k < R) keep[(int64_t)k * h_max + t] = src[k * s_k + t * s_t];
+            if (++k == Kb) { k = 0; ++t; }
+        }
+    } else {
+        const int v0 = (g - gm) * 8;
+        if (v0 >= nr) return;
+        bad = pack_group(hist + f.par * plane + row0, h_max, 1, f.K_r, v0, nr - v0 < 8 ? nr - v0 : 8, bits,
+                         pkt + 4 + main_bytes + (int64_t)(g - gm) * bits);
+    }
+    if (bad) atomicOr(err, 1);
+}
+
 // The inverse over all n_max * K code positions of every slot: lane g reads its bytes of the
 // payload only where the slot delivers the code, and writes 0 past the slot's count.
 __global__ void bitunpack_slots_kernel(const uint8_t* __restrict__ in, int64_t in_stride, int B, int K, int n_max,
@@ -254,6 +327,23 @@ int encx_bitpack_slots_nq(const int64_t* codes, int64_t s_b, int64_t s_k, int64_
     hipLaunchKernelGGL(bitpack_slots_kernel<true>, dim3((unsigned)cdiv(B * groups, 256)), dim3(256), 0,
                        (hipStream_t)stream, codes, s_b, s_k, s_t, (int)B, (int)K, (int)n_max, bits, slots, nq, out,
                        out_stride, nbytes, groups, err);
+    ENCX_CHECK_LAUNCH();
+    return 0;
+}
+
+int encx_bitpack_slots_fec(const int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t, int64_t B, int64_t K,
+                           int64_t n_max, int bits, int64_t R, int64_t h_max, const int32_t* slots, const int32_t* nq,
+                           const int32_t* fec, int64_t* hist, uint8_t* out, int64_t out_stride, int64_t* nbytes,
+                           int* err, encx_stream_t stream) {
+    ENCX_REQUIRE(codes && slots && nq && fec && hist && out && nbytes && err);
+    ENCX_REQUIRE(B >= 1 && B <= 64 && K >= 1 && K <= 64 && n_max >= 1 && n_max <= 255 && bits >= 1 && bits <= 32);
+    ENCX_REQUIRE(R >= 1 && R <= K && h_max >= n_max && h_max <= 255);
+    ENCX_REQUIRE(out_stride >= 4 + encx_bitpack_bytes(n_max * K, bits) + encx_bitpack_bytes(h_max * R, bits));
+    encx_prof_scope ps((hipStream_t)stream, 0.0, 9.0 * B * (K * n_max + 2 * R * h_max), "bitpack_slots_fec", false);
+    const int gm = (int)cdiv(n_max * K, 8), gr = (int)cdiv(h_max * R, 8);
+    hipLaunchKernelGGL(bitpack_slots_fec_kernel, dim3((unsigned)cdiv(B * (gm + gr), 256)), dim3(256), 0,
+                       (hipStream_t)stream, codes, s_b, s_k, s_t, (int)B, (int)K, (int)n_max, bits, (int)R,
+                       (int)h_max, slots, nq, fec, hist, out, out_stride, nbytes, gm, gr, err);
     ENCX_CHECK_LAUNCH();
     return 0;
 }

@@ -61,6 +61,34 @@ def check_n_q(frames, n_q, n_q_max: int) -> tp.List[int]:
     return out
 
 
+def check_fec(frames, fec, fec_max: int) -> tp.List[int]:
+    """fec[b] = the most codebooks of its previous packet slot b's packet repeats this step: an int
+    in 0..fec_max (0: no copy) for a slot that delivers frames; whatever stands at a slot with 0
+    frames is ignored. None: fec_max for every slot. -> the counts, 0 at the slots that sit out.
+    Raises ValueError; host data only."""
+    if fec is None:
+        return [fec_max if f else 0 for f in frames]
+    try:
+        fec = list(fec)
+    except TypeError:
+        raise ValueError('encx streaming: fec must be a sequence of ints') from None
+    if len(fec) != len(frames):
+        raise ValueError(f'encx streaming: fec for {len(fec)} slots, the step has {len(frames)}')
+    out = []
+    for b, (f, r) in enumerate(zip(frames, fec)):
+        if not f:
+            out.append(0)
+            continue
+        try:
+            r = operator.index(r)
+        except TypeError:
+            raise ValueError(f'encx streaming: fec of slot {b} is not an int') from None
+        if not 0 <= r <= fec_max:
+            raise ValueError(f'encx streaming: fec {r} in slot {b} (0..{fec_max})')
+        out.append(r)
+    return out
+
+
 def check_restart(slots, batch: int) -> tp.List[int]:
     """The slot indices of a restart(), each in 0..batch-1 (ValueError otherwise)."""
     slots = _ints(slots, 'slots')

@@ -118,7 +118,35 @@ LM-coded streams: after a lost packet the receiver's LM context differs from the
 unpacker.lose([b]) marks the slot failed and drops its packets unread (0 frames) while the decoder
 conceals; once the sender knows, packer.restart([b]) and unpacker.restart([b]) restart the LM
 context only. Encoder and decoder are NOT restarted. Not here: codes predicted by the LM for the
-lost frames, redundancy in the packets, sequence numbers (detecting a loss is the transport's job).
+lost frames, sequence numbers (detecting a loss is the transport's job).
+
+Redundant packets (raw form). The first K_r codebooks of a frame are a coarser description of the
+same frame, so a packet may repeat them for the slot's previous packet (in-band FEC; the format is
+REDUNDANT PACKET in include/encx.h). A receiver that holds the next packet decodes a lost step at
+K_r codebooks with the decoder it has, instead of concealing it:
+
+    packer = StreamPacker(model, 64, 32, slot_n_q=True, fec=2)          # up to 2 codebooks repeated
+    unpacker = StreamUnpacker(model, 64, 32, slot_n_q=True, fec=2)
+    packets = packer.pack_slots(codes, frames, nq)                  # fec=[...]: 0..2 per slot, 0 = no copy
+    codes, frames, nq = unpacker.unpack_slots(packets)              # the main sections
+    codes, frames, nq = unpacker.unpack_slots(next_packets, recover=[b == 5 for b in range(64)])
+    wav, status = StreamReceiver(dec, unpacker).step(packets, ahead, lost_frames)   # the recipe as code
+
+The packer is still one launch per step: it keeps rows < R of each slot's last packet on the
+device, in two copies that a slot alternates between, so the launch that reads a copy never
+writes it, and a step that raises leaves the last good one in place. A copy costs 2 header bytes
+and ceil(n_r K_r bits / 8). "Previous" is the slot's last step with frames; restart([b]) and
+reset() drop it. Not here: redundancy for LM-coded packets, more than one step of lookback.
+
+Key packets (LM-coded, lm_format=2). Bit 7 of header byte 1 says "this slot's LM context starts
+anew with this packet"; the unpacker then restarts the context itself, and takes the slot out of
+the lost and failed sets. The context is worth little (the packets table), so on a
+one-way link (broadcast, a recording tap) the sender sets the bit every few packets and a loss
+heals itself: unpacker.lose([b]), conceal while the slot's packets are dropped, and rejoin at the
+next key packet, with no word from the receiver.
+
+    packer = StreamPacker(model, 64, 32, use_lm=True, lm_format=2, key_interval=8)
+    packets = packer.pack_slots(codes, frames, nq, key=[...])       # key: B bools, OR-ed with the interval
 
 Inference only. Weight-normed weights are prepared once, at construction; call
 refresh_weights() after changing the model. reset() restarts every slot.
@@ -134,7 +162,7 @@ from torch import nn
 from . import ops
 from ._lib import call, stream, ensure_device
 from .lm import LMStreamEncoder, LMStreamDecoder
-from .slots import DeviceTable, _ints, check_frames, check_n_q, check_restart  # noqa: F401 (re-exported)
+from .slots import DeviceTable, _ints, check_fec, check_frames, check_n_q, check_restart  # noqa: F401 (re-exported)
 from .modules.conv import SConv1d, SConvTranspose1d
 from .modules.lstm import SLSTM
 from .modules.seanet import SEANetEncoder, SEANetResnetBlock
@@ -1015,14 +1043,41 @@ def packet_bytes_nq(n: int, K: int, bits: int) -> int:
     return 2 + (n * K * bits + 7) // 8
 
 
+def packet_bytes_fec(n: int, K: int, n_r: int, K_r: int, bits: int) -> int:
+    """Length of a redundant packet: the four header bytes (n, K, n_r, K_r), ceil(n K bits / 8) for
+    this step and, from the next byte on, ceil(n_r K_r bits / 8) for the copy of the previous one."""
+    return 4 + (n * K * bits + 7) // 8 + (n_r * K_r * bits + 7) // 8
+
+
+KEY_BIT = 0x80  # header byte 1 of packet format 2 (include/encx.h: KEY PACKET)
+
+
+def check_key(use_lm: bool, lm_format: int):
+    """Key packets exist in packet format 2 only: format 1 is the reference's header byte and has
+    no spare bit, and a raw packet carries no context to restart. Raises ValueError; host only."""
+    if not use_lm or lm_format != 2:
+        raise ValueError('encx streaming: key packets (key, key_interval) go with use_lm=True, lm_format=2')
+
+
 class _Packets:
     """What StreamPacker and StreamUnpacker share: the arguments, the LM session behind the
     LM-coded form, and for the raw form a slot table and byte buffers on the device, made at the
     first valid step (every refusal of a step's arguments is a pure host check). slot_n_q: the
     variable-bandwidth packets (two header bytes, K per slot from an nq table); n_q is then the
-    largest K."""
+    largest K. fec: the redundant packets (four header bytes, a copy of up to fec codebooks of the
+    slot's previous packet)."""
 
-    def __init__(self, model, batch, n_q, use_lm, lm, max_frames, graphs, lm_session, slot_n_q=False, lm_format=1):
+    def __init__(self, model, batch, n_q, use_lm, lm, max_frames, graphs, lm_session, slot_n_q=False, lm_format=1,
+                 fec=None):
+        if fec is not None:
+            if use_lm:
+                _refuse('redundant packets under the LM (a redundant copy would need an LM context of its own)')
+            if not slot_n_q:
+                raise ValueError('encx streaming: fec goes with slot_n_q=True (the copy has a codebook count of its own)')
+            fec = operator.index(fec)
+            if not 1 <= fec <= n_q:
+                raise ValueError(f'encx streaming: fec {fec} (1..n_q={n_q})')
+        self.fec = fec
         if use_lm and slot_n_q:
             _refuse('LM-coded packets with a per-slot n_q are not slot_n_q=True (the raw two-byte-header form) '
                     'with use_lm=True: pass use_lm=True, lm_format=2')
@@ -1070,6 +1125,8 @@ class _Packets:
                 raise RuntimeError('encx streaming runs on the GPU (no CPU fallback): move the model first')
             ensure_device(dev)
             self._stride = self._packet_bytes(self.max_frames, self.n_q, self.bits)
+            if self.fec is not None:
+                self._stride = packet_bytes_fec(self.max_frames, self.n_q, self.max_frames, self.fec, self.bits)
             self._slots = DeviceTable(self.B, 2, dev)
             self._nq = DeviceTable(self.B, 1, dev)
             self._bytes = torch.zeros(self.B, self._stride, dtype=torch.uint8, device=dev)
@@ -1098,26 +1155,102 @@ class StreamPacker(_Packets):
     None), the LM's context carried across a slot's packets (encx.lm.LMStreamEncoder). The
     packet format is documented in include/encx.h. Slot b's codes past frames[b] are not read.
     use_lm=True, lm_format=2: pack_slots(codes, frames, n_q), the LM-coded packet with a codebook
-    count per slot and step (two header bytes, short flush; n_q is then the session's largest)."""
+    count per slot and step (two header bytes, short flush; n_q is then the session's largest);
+    key_interval=N: every N-th packet of a slot, its first included, is a key packet.
+    slot_n_q=True, fec=R (1..n_q): redundant packets, each with a copy of up to R codebooks of the
+    slot's previous packet (module docstring)."""
 
     def __init__(self, model, batch: int, n_q: int, use_lm: bool = False, lm=None, max_frames: int = 8,
-                 graphs: bool = True, slot_n_q: bool = False, lm_format: int = 1):
-        super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamEncoder, slot_n_q, lm_format)
+                 graphs: bool = True, slot_n_q: bool = False, lm_format: int = 1, fec: tp.Optional[int] = None,
+                 key_interval: tp.Optional[int] = None):
+        if key_interval is not None:
+            check_key(use_lm, lm_format)
+            key_interval = operator.index(key_interval)
+            if key_interval < 1:
+                raise ValueError(f'encx streaming: key_interval {key_interval} (at least 1 packet)')
+        super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamEncoder, slot_n_q, lm_format, fec)
+        self.key_interval = key_interval
+        self._sent = [0] * self.B              # key packets: the slot's packets since its stream began
+        self._owed: tp.Set[int] = set()        # key packets: slots restarted by a step that then raised
+        self._prev = [(0, 0)] * self.B         # fec: (frames, K) of the slot's previous packet, (0, 0) for none
+        self._par = [0] * self.B               # fec: the copy of the history that holds it (encx.h: fec[B][4])
+
+    def reset(self):
+        super().reset()
+        self._sent, self._prev = [0] * self.B, [(0, 0)] * self.B
+        self._owed.clear()
+
+    def restart(self, slots):
+        """As StreamEncoder.restart: the named slots' next packet begins a stream; it carries no
+        redundant copy, and it counts as the first of its stream for key_interval."""
+        super().restart(slots)
+        for b in check_restart(slots, self.B):
+            self._sent[b], self._prev[b] = 0, (0, 0)
+            self._owed.discard(b)
+
+    def _ensure(self):
+        fresh = self._dev is None
+        super()._ensure()
+        if fresh and self.fec is not None:
+            self._fec = DeviceTable(self.B, 4, self._dev)
+            self._hist = torch.zeros(2, self.B, self.fec, self.max_frames, dtype=torch.int64, device=self._dev)
+
+    def _keys(self, frames, key):
+        """The slots whose packet of this step is a key packet: every key_interval-th of a stream,
+        its first included, and those the caller names. Host data only."""
+        if key is None and self.key_interval is None:
+            return []
+        check_key(self.use_lm, self.lm_format)
+        frames = _ints(frames, 'frames')
+        if key is not None:
+            try:
+                key = [bool(v) for v in key]
+            except TypeError:
+                raise ValueError('encx streaming: key must be a sequence of bools') from None
+            if len(key) != self.B or len(frames) != self.B:
+                raise ValueError(f'encx streaming: key for {len(key)} slots, the session has {self.B}')
+        N = self.key_interval
+        return [b for b, f in enumerate(frames[:self.B])
+                if f and ((key is not None and key[b]) or (N is not None and self._sent[b] % N == 0)
+                          or b in self._owed)]
 
     @torch.no_grad()
-    def pack_slots(self, codes: torch.Tensor, frames: tp.Sequence[int],
-                   n_q: tp.Optional[tp.Sequence[int]] = None) -> tp.List[bytes]:
+    def pack_slots(self, codes: torch.Tensor, frames: tp.Sequence[int], n_q: tp.Optional[tp.Sequence[int]] = None,
+                   fec: tp.Optional[tp.Sequence[int]] = None, key: tp.Optional[tp.Sequence[bool]] = None) -> tp.List[bytes]:
         """slot_n_q=True: pack_slots(codes, frames, n_q) -> variable-bandwidth packets (include/encx.h):
         bytes (frames[b], n_q[b]) and the payload of codes[b, :n_q[b], :frames[b]]; rows k >= n_q[b]
-        are not read."""
+        are not read.
+
+        A packer built with fec=R: redundant packets. Each carries, behind its own codes, the first
+        K_r = min(R, the K of the slot's previous packet) codebooks of that packet; fec: B ints in
+        0..R, K_r = min(fec[b], previous K) instead, 0 for no copy (entries at slots with 0 frames
+        are ignored). One launch per step; a step that raises leaves the history as it was.
+
+        lm_format=2: key: B bools; a slot's packet is a key packet where key[b] is set or the
+        packer's key_interval says so: its LM context is restarted first and bit 7 of byte 1 set."""
         if (self.slot_n_q or self.lm_format == 2) != (n_q is not None):
             raise ValueError('encx streaming: n_q goes with slot_n_q=True or lm_format=2, and only with them')
+        if fec is not None and self.fec is None:
+            raise ValueError('encx streaming: fec goes with a packer built with fec=R')
+        keys = self._keys(frames, key)
         if self._lm is not None:
-            return self._lm.packets(codes, frames, n_q)
+            if keys:
+                # restarted here, flagged below: a step that raises in between still owes the flag
+                self._lm.restart(keys)
+                self._owed.update(keys)
+            packets = self._lm.packets(codes, frames, n_q)
+            for b in keys:
+                packets[b] = packets[b][:1] + bytes([packets[b][1] | KEY_BIT]) + packets[b][2:]
+            self._owed.difference_update(keys)
+            if self.key_interval is not None:
+                self._sent = [c + bool(p) for c, p in zip(self._sent, packets)]
+            return packets
         frames = _ints(frames, 'frames')
         n_max, _ = check_frames([True] * self.B, frames, 1, self.max_frames)
         if n_q is not None:
             n_q = check_n_q(frames, n_q, self.n_q)
+        if self.fec is not None:
+            fec = check_fec(frames, fec, self.fec)
         if codes.dim() != 3 or tuple(codes.shape) != (self.B, self.n_q, n_max) or codes.dtype != torch.int64:
             raise ValueError(f'encx streaming: expected int64 codes [{self.B}, {self.n_q}, max(frames) = {n_max}], '
                              f'got {codes.dtype} {tuple(codes.shape)}')
@@ -1127,13 +1260,30 @@ class StreamPacker(_Packets):
         nq = self._put(frames, n_q)
         self._err.zero_()
         sb, sk, s_t = codes.stride()
-        call('encx_bitpack_slots_nq' if nq else 'encx_bitpack_slots', codes.data_ptr(), sb, sk, s_t, self.B,
-             self.n_q, n_max, self.bits, self._slots.data_ptr(), *nq, self._bytes.data_ptr(), self._stride,
-             self._nbytes.data_ptr(), self._err.data_ptr(), stream())
+        if self.fec is not None:
+            # the copy: the previous packet's frames at min(fec[b], its K) codebooks, none at 0
+            red = [(n, min(r, K)) if min(r, K) else (0, 0) for r, (n, K) in zip(fec, self._prev)]
+            self._fec.put((n_r, K_r, par, 0) for (n_r, K_r), par in zip(red, self._par))
+            call('encx_bitpack_slots_fec', codes.data_ptr(), sb, sk, s_t, self.B, self.n_q, n_max, self.bits,
+                 self.fec, self.max_frames, self._slots.data_ptr(), *nq, self._fec.data_ptr(),
+                 self._hist.data_ptr(), self._bytes.data_ptr(), self._stride, self._nbytes.data_ptr(),
+                 self._err.data_ptr(), stream())
+        else:
+            call('encx_bitpack_slots_nq' if nq else 'encx_bitpack_slots', codes.data_ptr(), sb, sk, s_t, self.B,
+                 self.n_q, n_max, self.bits, self._slots.data_ptr(), *nq, self._bytes.data_ptr(), self._stride,
+                 self._nbytes.data_ptr(), self._err.data_ptr(), stream())
         host = self._bytes.cpu()
         if int(self._err.item()):
             raise ValueError(f'encx streaming: a delivered code does not fit in {self.bits} bits')
-        size, bits = self._packet_bytes, self.bits
+        bits = self.bits
+        if self.fec is not None:
+            # the slots that delivered now read the copy of the history this step wrote
+            for b, (f, q) in enumerate(zip(frames, n_q)):
+                if f:
+                    self._prev[b], self._par[b] = (f, q), self._par[b] ^ 1
+            return [host[b, :packet_bytes_fec(f, q, n_r, K_r, bits)].numpy().tobytes() if f else b''
+                    for b, (f, q, (n_r, K_r)) in enumerate(zip(frames, n_q, red))]
+        size = self._packet_bytes
         return [host[b, :size(f, q, bits)].numpy().tobytes() if f else b''
                 for b, (f, q) in enumerate(zip(frames, n_q or [self.n_q] * self.B))]
 
@@ -1145,11 +1295,14 @@ class StreamUnpacker(_Packets):
     and zero codes, is listed in `failed`, and refuses packets until restart([b]).
     use_lm=True, lm_format=2: -> (codes [B, n_q, max(frames)], frames, n_q) from the LM-coded
     packets with a count per slot, ready for StreamDecoder.decode_slots(codes, frames, n_q=n_q); a
-    failed slot comes back with 0 frames, 0 codebooks and zero codes."""
+    failed slot comes back with 0 frames, 0 codebooks and zero codes; a key packet restarts its
+    slot's LM context in band.
+    slot_n_q=True, fec=R: redundant packets; unpack_slots(packets, recover=[...]) decodes the copy
+    of a lost step from the slot's next packet."""
 
     def __init__(self, model, batch: int, n_q: int, use_lm: bool = False, lm=None, max_frames: int = 8,
-                 graphs: bool = True, slot_n_q: bool = False, lm_format: int = 1):
-        super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamDecoder, slot_n_q, lm_format)
+                 graphs: bool = True, slot_n_q: bool = False, lm_format: int = 1, fec: tp.Optional[int] = None):
+        super().__init__(model, batch, n_q, use_lm, lm, max_frames, graphs, LMStreamDecoder, slot_n_q, lm_format, fec)
 
     @property
     def failed(self) -> tp.List[int]:
@@ -1169,12 +1322,20 @@ class StreamUnpacker(_Packets):
             self._lost.update(slots)
             self._lm.lose(slots)
 
-    def _drop_lost(self, packets):
+    def _key_slots(self, packets):
+        """The slots whose packet has the key bit set (packet format 2 only; a packet that is not
+        bytes, or has no byte 1, is left to _headers)."""
+        if self.lm_format != 2:
+            return []
+        return [b for b, p in enumerate(packets)
+                if isinstance(p, (bytes, bytearray)) and len(p) >= 2 and p[1] & KEY_BIT]
+
+    def _drop_lost(self, packets, keys=()):
         """The packets with those of the lost slots replaced by b'' (unread), or None when that
-        leaves no packet at all."""
+        leaves no packet at all. keys: slots whose packet is a key packet; it is read."""
         if not self._lost or len(packets) != self.B:
             return packets
-        kept = [b'' if b in self._lost else p for b, p in enumerate(packets)]
+        kept = [b'' if b in self._lost and b not in keys else p for b, p in enumerate(packets)]
         if any(len(p) for p in packets if isinstance(p, (bytes, bytearray))) and \
                 not any(len(p) for p in kept if isinstance(p, (bytes, bytearray))):
             return None
@@ -1195,6 +1356,8 @@ class StreamUnpacker(_Packets):
                 if len(p) < hdr:
                     raise ValueError(f'encx streaming: the packet of slot {b} has no (n, K) header')
                 n, K = p[0], p[1] if hdr == 2 else K_max
+                if self.lm_format == 2:
+                    K &= ~KEY_BIT
                 if not 1 <= n <= self.max_frames:
                     raise ValueError(f'encx streaming: the packet of slot {b} announces {n} frames '
                                      f'(1..max_frames={self.max_frames})')
@@ -1222,16 +1385,82 @@ class StreamUnpacker(_Packets):
                 host[b, :len(p)] = torch.frombuffer(bytearray(p), dtype=torch.uint8)
         self._bytes.copy_(host)
 
+    def _sections(self, packets, recover):
+        """The headers (n, K, n_r, K_r) of a step's redundant packets -> (frames, n_q, payloads):
+        per slot the section asked for, the main one or with recover[b] the copy of the slot's
+        previous packet, as the payload of a variable-bandwidth packet; (0, 0, b'') for b'' and for
+        a copy the packet does not carry. Raises ValueError; host data only."""
+        if len(packets) != self.B:
+            raise ValueError(f'encx streaming: packets for {len(packets)} slots, the session has {self.B}')
+        if recover is None:
+            recover = [False] * self.B
+        else:
+            try:
+                recover = [bool(v) for v in recover]
+            except TypeError:
+                raise ValueError('encx streaming: recover must be a sequence of bools') from None
+            if len(recover) != self.B:
+                raise ValueError(f'encx streaming: recover for {len(recover)} slots, the session has {self.B}')
+        frames, n_q, payloads = [], [], []
+        bits = self.bits
+        for b, p in enumerate(packets):
+            if not isinstance(p, (bytes, bytearray)):
+                raise ValueError(f'encx streaming: the packet of slot {b} is not bytes')
+            n = K = 0
+            pay = b''
+            if len(p):
+                if len(p) < 4:
+                    raise ValueError(f'encx streaming: the packet of slot {b} has no (n, K, n_r, K_r) header')
+                n, K, n_r, K_r = p[:4]
+                if not 1 <= n <= self.max_frames or n_r > self.max_frames:
+                    raise ValueError(f'encx streaming: the packet of slot {b} announces {n} frames and a copy of '
+                                     f'{n_r} (1..max_frames={self.max_frames})')
+                if not 1 <= K <= self.n_q or K_r > self.n_q:
+                    raise ValueError(f'encx streaming: the packet of slot {b} announces {K} codebooks and a copy of '
+                                     f'{K_r} (1..n_q={self.n_q})')
+                if (n_r == 0) != (K_r == 0):
+                    raise ValueError(f'encx streaming: the packet of slot {b} announces a copy of {n_r} frames of '
+                                     f'{K_r} codebooks')
+                if len(p) != packet_bytes_fec(n, K, n_r, K_r, bits):
+                    raise ValueError(f'encx streaming: a redundant packet of {n} x {K} and {n_r} x {K_r} codes in slot '
+                                     f'{b} has {packet_bytes_fec(n, K, n_r, K_r, bits)} bytes, not {len(p)}')
+                split = 4 + (n * K * bits + 7) // 8
+                if recover[b]:
+                    n, K, pay = n_r, K_r, bytes(p[split:])
+                else:
+                    pay = bytes(p[4:split])
+            frames.append(n)
+            n_q.append(K)
+            payloads.append(pay)
+        if not any(len(p) for p in packets):
+            raise ValueError('encx streaming: no slot delivers a frame')
+        return frames, n_q, payloads
+
     @torch.no_grad()
-    def unpack_slots(self, packets: tp.Sequence[bytes]):
+    def unpack_slots(self, packets: tp.Sequence[bytes], recover: tp.Optional[tp.Sequence[bool]] = None):
         """slot_n_q=True: -> (codes [B, n_q, max(frames)], frames, n_q) from variable-bandwidth
         packets, n_q[b] = 0 for an empty packet and zero rows at k >= n_q[b]: ready for
-        StreamDecoder.decode_slots(codes, frames, n_q)."""
-        packets = self._drop_lost(packets)
+        StreamDecoder.decode_slots(codes, frames, n_q).
+
+        An unpacker built with fec=R takes redundant packets and decodes their main sections.
+        recover: B bools; recover[b] says packets[b] is the slot's NEXT packet and the step before
+        it, which was lost, is wanted: the slot comes back with the frames, n_q and codes of the
+        redundant copy, (0, 0) and zero codes when the packet carries none.
+
+        lm_format=2: a key packet (bit 7 of byte 1) restarts the slot's LM context before it is
+        decoded and takes the slot out of the lost and failed sets, whether it was lost or not."""
+        if self.fec is not None:
+            return self._unpack_fec(packets, recover)
+        if recover is not None:
+            raise ValueError('encx streaming: recover goes with an unpacker built with fec=R')
+        keys = self._key_slots(packets)
+        packets = self._drop_lost(packets, keys)
         if packets is None:  # every packet of the step belongs to a lost slot: nothing to decode
             codes = torch.zeros(self.B, self.n_q, 0, dtype=torch.int64, device=next(self.model.parameters()).device)
             return (codes, [0] * self.B, [0] * self.B) if self.lm_format == 2 else (codes, [0] * self.B)
         frames, n_q = self._headers(packets)
+        if keys:  # an in-band restart([b]): the sender did restart, so this side does too
+            self.restart(keys)
         if self._lm is not None:
             codes, failed = self._lm.decode_slots([bytes(p[self._hdr:]) for p in packets], frames,
                                                   n_q if self._hdr == 2 else None)
@@ -1247,3 +1476,73 @@ class StreamUnpacker(_Packets):
                  self._stride, self.B, self.n_q, n_max, self.bits, self._slots.data_ptr(), *nq, codes.data_ptr(),
                  sb, sk, s_t, stream())
         return (codes, frames, n_q) if self._hdr == 2 else (codes, frames)
+
+    def _unpack_fec(self, packets, recover):
+        """unpack_slots for redundant packets: the host copies the section each slot asked for to
+        the start of its row of the staging buffer, and the variable-bandwidth unpacker reads it."""
+        frames, n_q, payloads = self._sections(packets, recover)
+        n_max = max(frames)
+        dev = next(self.model.parameters()).device
+        if not n_max:  # only copies were asked for, and no packet carries one
+            return torch.zeros(self.B, self.n_q, 0, dtype=torch.int64, device=dev), frames, n_q
+        self._ensure()
+        self._upload(payloads)
+        nq = self._put(frames, n_q)
+        codes = torch.empty(self.B, self.n_q, n_max, dtype=torch.int64, device=self._dev)
+        sb, sk, s_t = codes.stride()
+        call('encx_bitunpack_slots_nq', self._bytes.data_ptr(), self._stride, self.B, self.n_q, n_max, self.bits,
+             self._slots.data_ptr(), *nq, codes.data_ptr(), sb, sk, s_t, stream())
+        return codes, frames, n_q
+
+
+# ---------------------------------------------------------------------------- the receiver's recipe
+class StreamReceiver:
+    """What a receiver with a one-step jitter buffer does with redundant packets, as code:
+
+        rx = StreamReceiver(StreamDecoder(model, B, n_q), StreamUnpacker(model, B, n_q, slot_n_q=True, fec=R))
+        wav, status = rx.step(packets, ahead, lost_frames)
+
+    Per slot packets[b] is this step's packet, b'' for a slot that sits out, None for a packet
+    that did not arrive; ahead[b] is the slot's next packet where the jitter buffer already holds
+    it, else None; lost_frames[b] is the number of frames to conceal when nothing recovers the step
+    (the transport knows it from timing). A packet that is there is decoded from its main section;
+    a lost one from the redundant copy in ahead[b], at the copy's codebook count; where there is
+    none the decoder conceals lost_frames[b] frames. At most one unpack_slots and one decode_slots
+    call per step. -> (wav [B, C, max frames * hop], status): per slot 'main', 'recovered',
+    'concealed' or 'idle'. Sequence numbers and detecting a loss stay the transport's job."""
+
+    def __init__(self, decoder, unpacker):
+        self.decoder, self.unpacker = decoder, unpacker
+
+    def step(self, packets, ahead, lost_frames):
+        B = len(packets)
+        if len(ahead) != B or len(lost_frames) != B:
+            raise ValueError(f'encx streaming: packets for {B} slots, ahead for {len(ahead)}, lost_frames for '
+                             f'{len(lost_frames)}')
+        status = ['idle'] * B
+        chosen, recover = [b''] * B, [False] * B
+        for b, p in enumerate(packets):
+            if p is None:
+                status[b] = 'concealed'
+                if ahead[b] is not None and len(ahead[b]):
+                    chosen[b], recover[b] = ahead[b], True
+            elif len(p):
+                status[b], chosen[b] = 'main', p
+        codes, frames, n_q = None, [0] * B, [0] * B
+        if any(len(p) for p in chosen):
+            codes, frames, n_q = self.unpacker.unpack_slots(chosen, recover)
+            frames, n_q = list(frames), list(n_q)
+        lost = [False] * B
+        for b in range(B):
+            if recover[b] and frames[b]:
+                status[b] = 'recovered'
+            elif status[b] == 'concealed':
+                frames[b], n_q[b], lost[b] = operator.index(lost_frames[b]), 0, True
+        n_max = max(frames)
+        if codes is not None and not any(f and not gone for f, gone in zip(frames, lost)):
+            codes = None  # every slot with frames is concealed
+        elif codes is not None and codes.shape[2] < n_max:
+            # a concealed slot has more frames than any packet of the step: its columns are not read
+            codes = torch.nn.functional.pad(codes, (0, n_max - codes.shape[2]))
+        wav = self.decoder.decode_slots(codes, frames, n_q=n_q, lost=lost if any(lost) else None)
+        return wav, status

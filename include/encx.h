@@ -925,6 +925,44 @@ int encx_bitunpack_slots_nq(const uint8_t* in, int64_t in_stride, int64_t B, int
                             const int32_t* slots, const int32_t* nq, int64_t* codes, int64_t s_b, int64_t s_k,
                             int64_t s_t, encx_stream_t stream);
 
+/* ------------------------------------------- redundancy inside the raw packets (encx/streaming.py)
+ * The first K_r codebooks of a frame are a valid coarser description of that frame, so a packet may
+ * repeat them for the slot's previous packet (in-band FEC): a receiver that holds the next packet
+ * decodes a lost step at K_r codebooks with the decoder it has.
+ *
+ * REDUNDANT PACKET. The variable-bandwidth packet with a four-byte header and a second section:
+ *   byte 0     n    (1..255 latent frames of this step)
+ *   byte 1     K    (1..64 codebooks of this step)
+ *   byte 2     n_r  (0..255 frames of the redundant copy; 0: the packet carries none)
+ *   byte 3     K_r  (0..64 codebooks of the copy; 0 exactly when n_r is 0)
+ *   main       encx_bitpack_bytes(n*K, bits) bytes: byte for byte the payload of the variable-
+ *              bandwidth packet of this step
+ *   red        encx_bitpack_bytes(n_r*K_r, bits) bytes, starting on a byte boundary: the payload of
+ *              a variable-bandwidth packet of the slot's PREVIOUS delivered step, rows k < K_r
+ * "Previous" is the slot's last step with frames > 0; a step it sat out does not count, and the
+ * first packet of a stream carries no copy. One step of lookback only.
+ *
+ * encx_bitpack_slots_fec: encx_bitpack_slots_nq writing such packets, ONE launch for all slots. R
+ * (1..K) is the most codebooks a copy may have; hist is the history, int64 [2][B][R][h_max] (h_max:
+ * n_max..255, the session's largest step), owned by the packer and zero before its first step. A
+ * third device table beside slots[2B] and nq[B], int32 fec[B][4]:
+ *   word 0   n_r: the frames of the slot's previous packet (clamped to 0..h_max)
+ *   word 1   K_r: the codebooks of the copy (clamped to 0..R; either 0 means no copy)
+ *   word 2   par: hist[par & 1] holds the slot's previous packet
+ *   word 3   0
+ * For a slot that delivers, the launch writes the header, both sections and nbytes[b] = 4 + main +
+ * red, reads the copy from hist[par][b][k < K_r][t < n_r] and stores codes[b][k][t] for k < min(R,
+ * nq[b]), t < count into hist[par ^ 1][b]: no cell is read and written by the same launch. The host
+ * flips a slot's par after a step the slot delivered in, and only when *err stayed 0, so a refused
+ * step leaves the previous history valid. A slot that sits out gets nbytes[b] = 0 and nothing else
+ * is written for it. out_stride >= 4 + encx_bitpack_bytes(n_max*K, bits) + encx_bitpack_bytes(
+ * h_max*R, bits). The receiver needs no kernel of its own: the host hands the section it wants to
+ * encx_bitunpack_slots_nq. */
+int encx_bitpack_slots_fec(const int64_t* codes, int64_t s_b, int64_t s_k, int64_t s_t, int64_t B, int64_t K,
+                           int64_t n_max, int bits, int64_t R, int64_t h_max, const int32_t* slots, const int32_t* nq,
+                           const int32_t* fec, int64_t* hist, uint8_t* out, int64_t out_stride, int64_t* nbytes,
+                           int* err, encx_stream_t stream);
+
 /* ------------------------------------------- concealing a lost packet, per slot (encx/streaming.py)
  * A slot whose packet did not arrive decodes its LAST LATENT FRAME again for the `count` frames of the
  * step: after the end-of-step roll, column P-1 of the decoder's first window (P: that window's
@@ -1017,10 +1055,16 @@ int encx_ac_decode_slots(const uint8_t* data, int64_t stride, const int64_t* nby
 /* ------------------------------ LM-coded packets with a K per slot and step (encx/lm.py lm_format=2)
  * PACKET FORMAT 2.
  *   byte 0     n  (1..max_frames <= 255 latent frames)
- *   byte 1     K  (1..K_max codebooks of this packet)
+ *   byte 1     K  (1..K_max <= 64 codebooks of this packet) in bits 0..6; bit 7 is the KEY bit
  *   payload    one arithmetic-coder run over the n*K codes, t-major then codebook, total_range_bits 24,
  *              the cdfs of build_stable_quantized_cdf exactly as the LM form above, ended by the SHORT
  *              FLUSH; may be empty.
+ * KEY PACKET. Bit 7 of byte 1 set: the slot's LM context starts anew with this packet, on both sides
+ * (position and previous codes are taken as 0, as on a stream's first packet: no launch). The bytes
+ * behind the header are those of the first packet of a fresh stream on the same codes. A receiver
+ * that lost a packet drops the slot's packets until the next key packet and goes on from there: no
+ * back channel is needed. A sender that never sets the bit produces the packets it always did. The
+ * one-byte-header LM form (format 1) has no spare bit and no key packets.
  * SHORT FLUSH. After the last symbol the coder holds low <= high and W = max_bit + 1 pending bits
  * (oracle/ac_oracle.encode). With j the largest of 0..W for which v = ceil(low / 2^j) 2^j <= high, the
  * W bits of v are appended most significant first (j = 0, v = low, is the reference's flush), the

@@ -33,7 +33,18 @@ is faster than (a) by more than it. Bytes: the trained toy LM's payload bytes pe
 2, format 1 and raw at n = 1 and n = 8; a format-2 payload longer than the format-1 payload of the
 same packet stops the tool.
 
+Redundant packets (--fec). Raw packets that repeat the first R = 2 codebooks of the slot's previous
+packet (include/encx.h: REDUNDANT PACKET) at B = 64, n in {1, 8}, K = 8, every slot delivering:
+  fused         pack_slots of a packer built with fec=2: one launch writes header, both sections and
+                the history;
+  two_launches  what the code before it can do for the same bytes: pack_slots of a slot_n_q packer on
+                this step's codes, a second one on the kept codes of the previous step at 2 rows, and
+                the host concatenation header + payload + payload.
+The bytes of the two are compared before anything is timed. Same clock and rounds. The byte cost is
+arithmetic: 2 header bytes + ceil(n_r K_r bits / 8) per packet, printed beside the raw packet's size.
+
 python tools/stream_packet_bench.py [--rounds 5] [--out profiles/stream/stream_packets.json]
+python tools/stream_packet_bench.py --fec [--out profiles/stream/stream_packets_fec.json]
 python tools/stream_packet_bench.py --nq [--out profiles/stream/stream_packets_nq.json]
 python tools/stream_packet_bench.py --nq --trace   # only 20 eager pack + unpack steps of (a) and of (d) at
                                                    # B = 64, n = 8, K_max = 32, for a kernel trace of its own
@@ -233,6 +244,39 @@ def nq_bytes(torch, dev, steps=300, B=4, T=480):
     return res
 
 
+FEC_R = 2  # codebooks of the previous packet a --fec packet repeats
+
+
+def fec_row(torch, m, B, n, args):
+    """One n of --fec: the fused packer against two variable-bandwidth packs and a host join."""
+    from encx.streaming import StreamPacker, packet_bytes_nq, packet_bytes_fec
+    dev = next(m.parameters()).device
+    g = torch.Generator().manual_seed(7000 + n)
+    frames, nq, kr = [n] * B, [K] * B, [FEC_R] * B
+    prev, codes = (torch.randint(0, CARD, (B, K, n), generator=g).to(dev) for _ in range(2))
+    fused = StreamPacker(m, B, K, slot_n_q=True, fec=FEC_R)
+    main, red = StreamPacker(m, B, K, slot_n_q=True), StreamPacker(m, B, K, slot_n_q=True)
+    hdr = bytes([n, K, n, FEC_R])
+
+    def two_launches():
+        a, b = main.pack_slots(codes, frames, nq), red.pack_slots(prev, frames, kr)
+        return [hdr + p[2:] + q[2:] for p, q in zip(a, b)]
+
+    fused.pack_slots(prev, frames, nq)  # the history now holds `prev`; in the timed calls it holds `codes`
+    if fused.pack_slots(codes, frames, nq) != two_launches():
+        raise SystemExit('--fec: the fused packer and the two launches disagree on the bytes')
+    v = {'fused': lambda: fused.pack_slots(codes, frames, nq), 'two_launches': two_launches}
+    row = {'B': B, 'n': n, 'K': K, 'R': FEC_R}
+    row.update(measure(torch, v, args.rounds, args.min_seconds))
+    f, t = row['fused'], row['two_launches']
+    row['two_launches_over_fused'] = round(t['ms'] / f['ms'], 3)
+    row['fused_ahead_beyond_the_spreads'] = f['max'] < t['min']
+    row['bytes'] = {'variable_bandwidth_packet': packet_bytes_nq(n, K, BITS),
+                    'redundant_packet': packet_bytes_fec(n, K, n, FEC_R, BITS),
+                    'cost': 2 + (n * FEC_R * BITS + 7) // 8}
+    return row
+
+
 def markov(torch, B, T, seed):
     perm = torch.randperm(64, generator=torch.Generator().manual_seed(1234))
     g = torch.Generator().manual_seed(seed)
@@ -290,10 +334,12 @@ def main():
     ap.add_argument('--min-seconds', type=float, default=0.3)
     ap.add_argument('--trace', action='store_true', help='only a few B = 64, n = 1 steps, for a kernel trace')
     ap.add_argument('--nq', action='store_true', help='format-2 packets (a codebook count per slot) against format 1')
+    ap.add_argument('--fec', action='store_true', help='redundant packets: the fused packer against two launches')
     ap.add_argument('--out', type=str, default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, 'profiles', 'stream', 'stream_packets_nq.json' if args.nq else 'stream_packets.json')
+        name = 'stream_packets_fec.json' if args.fec else 'stream_packets_nq.json' if args.nq else 'stream_packets.json'
+        args.out = os.path.join(ROOT, 'profiles', 'stream', name)
 
     import torch
     if not torch.cuda.is_available():
@@ -310,6 +356,20 @@ def main():
     m = m.to(dev).eval()
     lm = LMModel(32, CARD, dim=200, num_layers=5, past_context=262).to(dev).eval()
 
+    if args.fec:
+        with torch.no_grad():
+            rows = [fec_row(torch, m, 64, n, args) for n in (1, 8)]
+        for row in rows:
+            print(json.dumps(row), flush=True)
+        res = {'metric': 'ms per pack step (host copy of the packets included) and bytes per packet',
+               'device': torch.cuda.get_device_name(0), 'B': 64, 'K': K, 'R': FEC_R, 'bits': BITS, 'rounds': args.rounds,
+               'timing': f'host clock around blocks of calls ending in a synchronise, >= {args.min_seconds} s per '
+                         'variant, variants alternating within a round, after warm-up',
+               'rows': rows}
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write(json.dumps(res, indent=1) + '\n')
+        return
     with torch.no_grad():
         if args.trace and args.nq:
             from encx.streaming import StreamPacker, StreamUnpacker
